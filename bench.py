@@ -7,6 +7,13 @@ G step against the updated D + Adam(G), the four logged losses read back) over a
 batch already resident in HBM.  Prints ONE JSON line (rank 0).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--res 512] [--dist-backend nccl|gloo]
+                  [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the line: the headline rate, `ms_per_step` and the
+  roofline figures read from the timed steps themselves.  --full adds the measurements that take runs of their
+  own after the timed steps: the same step under the exact-fp32 conv math (`fp32_math`) and the CPU oracle
+  (`cpu_baseline`); --no-fp32-math / --no-cpu-baseline drop either from a --full run.
+  --dump-outputs DIR writes what the last timed step computed (dump_outputs) as DIR/<name>.npy; the inputs and
+  the initial weights are seeded, so two builds run with the same arguments can be compared output for output.
   N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
        or plain `python bench.py --gpus N`: with WORLD_SIZE unset the parent starts the N ranks
        itself (launch_ranks) before anything touches the GPU, relays rank 0's JSON line and
@@ -256,6 +263,38 @@ def fp32_math_arm(B, R, dev, x, y, steps=5, warmup=1):
             "note": "same step, batch and seed on a fresh model; every conv on the exact-fp32 MFMA (157.3 TFLOP/s peak)"}
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20    # --dump-outputs: all files together stay below this
+
+
+def step_outputs(step_fn, losses):
+    """What a caller of the timed step holds after its last call: the logged losses it returns (read back to the
+    host as in the timed loop) and that step's images and attention masks, which the step object keeps for its
+    caller (PairedStep.last_output / last_mask, CycleStep.last)."""
+    outs = {"losses": losses}
+    for attr, name in (("last_output", "output"), ("last_mask", "mask")):
+        if getattr(step_fn, attr, None) is not None:
+            outs[name] = getattr(step_fn, attr)
+    outs.update(getattr(step_fn, "last", None) or {})
+    return outs
+
+
+def dump_outputs(dirname, outs):
+    """Write every tensor of `outs` as <dirname>/<name>.npy in float32 (NCHW element order), whole when all of
+    them fit into DUMP_BUDGET_BYTES together.  Otherwise the files share the budget equally: an array above its
+    share is written as a fixed sample of its flattened elements (sorted indices drawn without replacement from
+    numpy's default_rng(1234), the same for every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: t.detach().to("cpu", torch.float32).contiguous().numpy() for k, t in outs.items()}
+    share = DUMP_BUDGET_BYTES // len(arrays) - 1024        # the .npy header
+    fits = sum(a.nbytes + 1024 for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for name, a in sorted(arrays.items()):
+        if not fits and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _rccl_version():
     try:
         v = torch.cuda.nccl.version()
@@ -409,9 +448,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8, help="images per GPU")
     ap.add_argument("--res", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the measurements that take runs of their own: the "
+                         "fp32_math sub-record and the cpu_baseline (both on one rank only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (its losses, images and attention masks) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline sub-record")
     ap.add_argument("--no-fp32-math", action="store_true",
-                    help="skip the fp32_math sub-record (5 steps of the same step under the exact-fp32 conv math)")
+                    help="--full: skip the fp32_math sub-record (5 steps of the same step under the exact-fp32 "
+                         "conv math)")
     ap.add_argument("--timeout", type=float, default=0,
                     help="N > 1 self-launch: seconds before hung ranks are terminated (rc 124); 0 = 900 + 30 s per step")
     ap.add_argument("--cpu-threads", type=int, default=0)
@@ -528,9 +574,12 @@ def main():
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(step_fn, losses))
     math = _lib.get_conv_math()
     fp32_rec = None
-    if world == 1 and not (cycle or p2p) and loader is None and not args.no_fp32_math and math != "fp32":
+    if (args.full and world == 1 and not (cycle or p2p) and loader is None and not args.no_fp32_math
+            and math != "fp32"):
         fp32_rec = fp32_math_arm(B, R, dev, x, y)
     # split maths execute several 16-bit MFMA products per fp32 multiply-add: the roof for fp32
     # work is the 16-bit dense MFMA peak / products (the fp32 MFMA path's roof is 157.3)
@@ -639,7 +688,7 @@ def main():
         if fp32_rec is not None:
             fp32_rec["vs_headline"] = round(fp32_rec["value"] / img_s, 4)
             out["fp32_math"] = fp32_rec
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or int(os.environ.get("OMP_NUM_THREADS", 0)) or len(os.sched_getaffinity(0))
             out["cpu_baseline"] = cpu_baseline(R, threads, steps=1 if cycle or p2p else 3, workload=args.workload,
                                                batches=(1,) if cycle or p2p else (1, 8))
