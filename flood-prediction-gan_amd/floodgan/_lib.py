@@ -201,13 +201,16 @@ SIGNATURES = {
     "fg_sq_err_sum": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p],
     "fg_mask_confusion": [fg_view, fg_view, C.c_void_p, C.c_void_p],
     "fg_maxpool2": [fg_view, fg_view, C.c_void_p],
+    "fg_maxpool2_bwd": [fg_view, fg_view, fg_view, C.c_void_p, C.c_void_p],
+    "fg_bce_logits_workspace_doubles": [],
+    "fg_bce_logits": [fg_view, C.c_void_p, C.c_float, fg_view, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fg_tiff_probe": [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "fg_tiff_read": [C.c_char_p, C.c_void_p, C.c_longlong],
     "fg_tile_transform": [C.POINTER(fg_tile_batch), C.c_void_p],
 }
 RESTYPES = {"fg_bernoulli_mt_workspace_words": C.c_longlong, "fg_last_error": C.c_char_p, "fg_last_launch": C.c_char_p, "fg_in_workspace_doubles": C.c_longlong, "fg_bn_workspace_doubles": C.c_longlong,
             "fg_ssim_workspace_doubles": C.c_longlong, "fg_sq_err_workspace_doubles": C.c_longlong,
-            "fg_channel_sum_workspace_doubles": C.c_longlong,
+            "fg_channel_sum_workspace_doubles": C.c_longlong, "fg_bce_logits_workspace_doubles": C.c_longlong,
             "fg_in_partials_workspace_doubles": C.c_longlong, "fg_conv1x1_wgrad_workspace_floats": C.c_longlong}
 
 _lib = None

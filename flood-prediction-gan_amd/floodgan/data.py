@@ -11,6 +11,9 @@ device-side transform of the reference's dataset (models/data.py:11-146, models/
                             np.fliplr, topography channels, bicubic antialias Resize, quadrant
                             crop, Normalize(0.5, 0.5)) writing channels-last tensors
   create_flood_dataset      models/data.py:11-44
+  determine_masks_dataset, MaskDataset, create_masks_dataset
+                            models/data.py:148-218: the segmentation model's labelled tiles (host decode; plain
+                            DataLoaders, as the reference)
 
 There is no CPU transform path: the loader needs a HIP device, like the rest of floodgan.
 """
@@ -495,3 +498,59 @@ def create_flood_dataset(dataset_subset, dataset_dem, path, topography, resize=N
         out.append(TileLoader(ds, batch_size=batch_size, shuffle=True, device=device, prefetch=prefetch,
                               workers=max(1, num_workers) if num_workers else 4, rank=rank, world=world))
     return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------ flood masks
+
+def determine_masks_dataset(subset, train_on_all, csv_path="metadata/masks_metadata.csv"):
+    """models/data.py:203-218: (train, validation, test) lists of (image file, version) from the masks table (read
+    relative to the working directory, as determine_flood_dataset reads its table); train_on_all: every image of
+    the subset as the training list, (list, None, None)"""
+    import pandas as pd
+    masks_split = pd.read_csv(csv_path)
+    if subset.lower() not in LOCATIONS:
+        raise NotImplementedError("Unrecognised dataset subset name")
+    ds = masks_split[masks_split["country"] == subset.lower()]
+    if train_on_all:
+        return list(zip(ds["image"], ds["version"])), None, None
+    return tuple(list(zip(ds[ds["split"] == n]["image"], ds[ds["split"] == n]["version"]))
+                 for n in ("train", "validation", "test"))
+
+
+class MaskDataset(torch.utils.data.Dataset):
+    """models/data.py:179-201: (image [3, H, W], mask [1, H, W], file name) of the segmentation model's labelled
+    tiles -- masks_input/*.tif (H x W x 3) and masks_output/*.tif (H x W), decoded by read_tile, np.fliplr applied
+    to both for the "flipped" version"""
+
+    def __init__(self, data, path):
+        self.data_files, self.path = data, path
+
+    def __getitem__(self, index):
+        image_path, version = self.data_files[index][0], self.data_files[index][1]
+        image = read_tile(f"{self.path}/masks_input/{image_path}")
+        mask = read_tile(f"{self.path}/masks_output/{image_path}")
+        if mask.shape[2] != 1:
+            raise ValueError(f"MaskDataset: {image_path}: the mask tile must be 2-D (got {mask.shape[2]} channels)")
+        mask = mask[:, :, 0]
+        if version == "flipped":
+            image, mask = np.fliplr(image), np.fliplr(mask)
+        return (torch.from_numpy(image.transpose(2, 0, 1).copy()), torch.from_numpy(mask.copy()).unsqueeze(dim=0),
+                image_path)
+
+    def __len__(self):
+        return len(self.data_files)
+
+
+def create_masks_dataset(dataset_subset, path, train_on_all, batch_size=1, num_workers=0,
+                         csv_path="metadata/masks_metadata.csv"):
+    """models/data.py:148-177: (train, validation, test) DataLoaders (shuffled, pinned) over MaskDataset; only the
+    training loader when train_on_all"""
+    train_data, val_data, test_data = determine_masks_dataset(dataset_subset, train_on_all, csv_path)
+
+    def loader(data):
+        return DataLoader(dataset=MaskDataset(data, path), batch_size=batch_size, num_workers=num_workers,
+                          shuffle=True, pin_memory=torch.cuda.is_available())
+
+    if train_on_all:
+        return loader(train_data), None, None
+    return loader(train_data), loader(val_data), loader(test_data)

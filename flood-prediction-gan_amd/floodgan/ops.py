@@ -1004,6 +1004,36 @@ def maxpool2(src, dst):
     L.check(_lib().fg_maxpool2(view(src), view(dst), L.stream_handle()), "maxpool2")
 
 
+def maxpool2_bwd(src, g_pooled, g_src, choice=None):
+    """g_src = the gradient of maxpool2(src) given g_pooled, routed to the first maximum of each 2x2 window (ATen's
+    rule); choice (optional uint8 [n, h / 2, w / 2, c] tensor): the chosen window position 0..3 per pooled element"""
+    if choice is not None:
+        want = (src.n, src.h // 2, src.w // 2, src.c)
+        if not isinstance(src, Buf) or choice.dtype != torch.uint8 or tuple(choice.shape) != want \
+                or not choice.is_contiguous() or choice.device != src.t.device:
+            raise RuntimeError(f"maxpool2_bwd: choice must be a contiguous uint8 tensor of shape {want} on the "
+                               f"source Buf's device (got {choice.dtype} {tuple(choice.shape)})")
+    _wrote(g_src)
+    L.check(_lib().fg_maxpool2_bwd(view(src), view(g_pooled), view(g_src), L.ptr(choice), L.stream_handle()),
+            "maxpool2_bwd")
+
+
+def bce_logits(logits, target, gscale, grad, loss_out, correct_out=None):
+    """loss_out[0] = BCEWithLogitsLoss()(logits channel 0, target [N, 1, H, W]); grad (Buf) channel 0 =
+    gscale * dL-sum/dz = (sigmoid(z) - t) * gscale, everything else in it zero; correct_out[0] (int64) = the count
+    of (sigmoid(z) > 0.5) == (t > 0.5)"""
+    L.require_device(target, "segmentation target")
+    if not target.is_contiguous() or target.numel() != logits.n * logits.h * logits.w:
+        raise RuntimeError(f"bce_logits: the target must be a contiguous [N, 1, H, W] tensor matching the logits "
+                           f"(got {tuple(target.shape)} for {logits.n}x1x{logits.h}x{logits.w})")
+    assert isinstance(grad, Buf) and loss_out.dtype == torch.float32
+    assert correct_out is None or correct_out.dtype == torch.int64
+    work = torch.empty(int(_lib().fg_bce_logits_workspace_doubles()), dtype=torch.float64, device=target.device)
+    _wrote(grad)
+    L.check(_lib().fg_bce_logits(view(logits), L.ptr(target), C.c_float(gscale), view(grad), L.ptr(loss_out),
+                                 L.ptr(correct_out), L.ptr(work), L.stream_handle()), "bce_logits")
+
+
 # ------------------------------------------------------------------ tail / losses / adam
 
 def tail_fwd(cl, al, x, out, mask):

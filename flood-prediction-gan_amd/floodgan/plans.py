@@ -143,6 +143,15 @@ def wmap_conv_dgrad_s1(shape, c_alloc_gy):
                  [kw - 1 - s for s in range(kw)])
 
 
+def wmap_conv_dgrad_s1_part(shape, c_alloc_gy, n_base, n_out):
+    """wmap_conv_dgrad_s1 restricted to the input channels n_base .. n_base + n_out: the gradient of one channel
+    slice of a conv's input (the halves of the segmentation U-Net's torch.cat, models/model_architectures.py:579)"""
+    O, I, kh, kw = shape
+    assert 0 <= n_base and n_base + n_out <= I
+    return _wmap(n_out, kh, kw, c_alloc_gy, O, 0, shape, [kh - 1 - r for r in range(kh)],
+                 [kw - 1 - s for s in range(kw)], n_base)
+
+
 def phase_taps(k, p, ph):
     """Stride-2 sub-pixel decomposition.  Output index 2a+ph of  y[o] = sum_{2i-p+r=o} x[i] w[r]
     reads x[a + d] for taps r = ph + p - 2d, d = dmin .. dmin+len-1.  Returns (dmin, [r...])."""

@@ -14,10 +14,24 @@ level's max-pool source and, for x1..x4, into the first channel half of the matc
 cat buffer (torch.cat([x2, x1], 1) of Up.forward, :579).  Each decoder level's ConvTranspose2d(2, 2)
 (one tap per output phase: four 1x1 GEMMs, bias fused) writes straight into the second half.  The
 1x1 OutConv produces the logits; the flood mask is sigmoid(logits) > 0.5.
+
+Training (models/segmentation_model.py:250-277).  unet_logits(save=True) keeps, per DoubleConv, its input, both
+conv outputs with their batch statistics and the first activation, and per level the activated output; under
+torch.no_grad() nothing is kept.  unet_backward walks the graph in reverse: OutConv (1x1, fp32 FMA kernels), then per
+decoder level the DoubleConv (BatchNorm backward through the batch statistics with the ReLU folded in, 3x3 weight and
+input gradients on the conv engine) whose input gradient -- the gradient of the cat -- is produced as its two channel
+halves in one launch: the skip half waits for the encoder, the other half goes through the ConvTranspose2d(2, 2)
+backward (input gradient: one k=2, stride-2 GEMM with K = 4 C_out; weight gradient; bias = channel sums).  Each
+encoder level's last BatchNorm backward sums its two consumers' gradients: the max-pool's (fg_maxpool2_bwd: first
+maximum of the window, ATen's tie rule) and the skip's.
 """
+import time
+
+import numpy as np
 import torch
 import torch.nn as nn
 
+from . import executor as X
 from . import ops
 from . import pix2pix as P2P
 from . import plans as PL
@@ -46,8 +60,9 @@ def check_input_size(H, W):
                            "does not implement")
 
 
-def _double_conv(P, B, names, X, mid, out, training, dsts):
-    """DoubleConv over X (zero border 1): returns nothing; dsts = (dst0, dst1) of the second ReLU"""
+def _double_conv(P, B, names, X, mid, out, training, dsts, save=None):
+    """DoubleConv over X (zero border 1): returns nothing; dsts = (dst0, dst1) of the second ReLU.  save (dict):
+    receives what _double_conv_bwd reads"""
     c1, b1, c2, b2 = names
     N, h, w = X.n, X.h, X.w
     dev = X.t.device
@@ -58,9 +73,11 @@ def _double_conv(P, B, names, X, mid, out, training, dsts):
     ops.bn_apply(t, 1, mean, invstd, P[b1 + ".weight"], P[b1 + ".bias"], None, FG_ACT_RELU, a)
     u = Buf.empty(N, h, w, out, 0, dev)
     P2P._conv_nb(P, c2, a, 1, 3, 1, u)
-    mean, invstd = P2P._stats(B, b2, u, 1, training)
-    ops.bn_apply(u, 1, mean, invstd, P[b2 + ".weight"], P[b2 + ".bias"], None, FG_ACT_RELU, dsts[0],
+    mean2, invstd2 = P2P._stats(B, b2, u, 1, training)
+    ops.bn_apply(u, 1, mean2, invstd2, P[b2 + ".weight"], P[b2 + ".bias"], None, FG_ACT_RELU, dsts[0],
                  FG_ACT_RELU if dsts[1] is not None else 0, dsts[1])
+    if save is not None:
+        save.update(x=X, t=t, m1=mean, i1=invstd, a=a, u=u, m2=mean2, i2=invstd2)
 
 
 def _convT2(P, name, X, Y):
@@ -71,37 +88,160 @@ def _convT2(P, name, X, Y):
     ops.conv(PL.phase_problems(X, w.shape, 2, 0, Y, wps, maps, bias=P.get(name + ".bias")))
 
 
-def unet_logits(P, B, X0, training=True):
+def unet_logits(P, B, X0, training=True, save=False):
     """Forward of UNet(3, 1) over X0 (Buf: the [0, 1] image in channels 0..2 of 4, zero border 1).
-    Returns the logits Buf [N, H, W, 4] (channel 0)."""
+    Returns the logits Buf [N, H, W, 4] (channel 0); with save=True, (logits, S): S holds the activations
+    unet_backward reads (nothing is kept otherwise)."""
     N, H, W = X0.n, X0.h, X0.w
     check_input_size(H, W)
     dev = X0.t.device
     enc, dec, head = layer_names()
+    S = dict(N=N, H=H, W=W, training=training, enc=[{} for _ in range(5)], dec=[{} for _ in range(4)]) if save \
+        else None
     cats = [Buf.zeros(N, H >> k, W >> k, 2 * ENC[k], 1, dev) for k in range(4)]     # decoder inputs by level
     X = X0
     for k in range(5):
         h, w = H >> k, W >> k
         if k < 4:
             x = Buf.empty(N, h, w, ENC[k], 0, dev)                 # max-pool source
-            _double_conv(P, B, enc[k], X, ENC[k], ENC[k], training, (x, Slice(cats[k], 0, ENC[k])))
+            _double_conv(P, B, enc[k], X, ENC[k], ENC[k], training, (x, Slice(cats[k], 0, ENC[k])),
+                         S["enc"][k] if save else None)
             X = Buf.zeros(N, h // 2, w // 2, ENC[k], 1, dev)
             ops.maxpool2(x, X)
         else:
-            x5 = Buf.zeros(N, h, w, ENC[k], 1, dev)
-            _double_conv(P, B, enc[k], X, ENC[k], ENC[k], training, (x5, None))
-            X = x5
+            x = Buf.zeros(N, h, w, ENC[k], 1, dev)
+            _double_conv(P, B, enc[k], X, ENC[k], ENC[k], training, (x, None), S["enc"][k] if save else None)
+            X = x
+        if save:
+            S["enc"][k]["out"] = x                                 # the level output (k < 4: the max-pool source)
     for i, (up, names) in enumerate(dec):                            # up1 .. up4
         k = 3 - i                                                    # the encoder level it joins
         c = ENC[k]
         _convT2(P, up, X, Slice(cats[k], c, c))
         last = i == len(dec) - 1
         y = Buf.zeros(N, H >> k, W >> k, c, 0 if last else 1, dev)
-        _double_conv(P, B, names, cats[k], c, c, training, (y, None))
+        _double_conv(P, B, names, cats[k], c, c, training, (y, None), S["dec"][i] if save else None)
+        if save:
+            S["dec"][i].update(xin=X, out=y)                       # the ConvTranspose input, the level output
         X = y
     logits = Buf.empty(N, H, W, 4, 0, dev)
     P2P._conv_nb(P, head, X, 0, 1, 1, logits)
-    return logits
+    return (logits, S) if save else logits
+
+
+def _double_conv_bwd(P, G, names, D, gA, gB=None, need_input=True, split=None):
+    """Backward of _double_conv from its saved tensors D.  The gradient of the DoubleConv's output is
+    gA * relu' (+ gB * relu': an encoder level's two consumers).  Returns the input gradient (None when not
+    needed: inc's image), as one Buf or, with split=c, as the two Bufs of its channels [0, c) and [c, 2c) (a decoder
+    level's cat: the skip half and the ConvTranspose half), both written by one launch."""
+    c1, b1, c2, b2 = names
+    u, t, a, x = D["u"], D["t"], D["a"], D["x"]
+    N, h, w = u.n, u.h, u.w
+    dev = u.t.device
+    g_u = Buf.empty(N, h, w, u.c, 1, dev)                  # zero border 1: the full correlation of a 3x3, pad 1
+    ops.bn_bwd(gA, FG_ACT_RELU, gB, FG_ACT_RELU if gB is not None else 0, u, 1, D["m2"], D["i2"], P[b2 + ".weight"],
+               P[b2 + ".bias"], None, g_u, G.get(b2 + ".weight"), G.get(b2 + ".bias"), G.acc)
+    ops.zero_border(g_u)
+    X._wgrad_conv(P, G, c2, g_u, a, 1, 3, 1)
+    g_a = Buf.empty(N, h, w, a.c, 0, dev)
+    X._dgrad_s1(P, c2, g_u, 1, 3, g_a)
+    g_t = Buf.empty(N, h, w, t.c, 1, dev)
+    ops.bn_bwd(g_a, FG_ACT_RELU, None, 0, t, 1, D["m1"], D["i1"], P[b1 + ".weight"], P[b1 + ".bias"], None, g_t,
+               G.get(b1 + ".weight"), G.get(b1 + ".bias"), G.acc)
+    ops.zero_border(g_t)
+    X._wgrad_conv(P, G, c1, g_t, x, 1, 3, 1)
+    if not need_input:
+        return None
+    wt = P[c1 + ".weight"]
+    if split is None:
+        g_x = Buf.empty(N, h, w, x.c, 0, dev)
+        X._dgrad_s1(P, c1, g_t, 1, 3, g_x)
+        return g_x
+    assert x.c == 2 * split
+    halves, probs = [], []
+    for c0 in (0, split):
+        g_h = Buf.empty(N, h, w, split, 0, dev)
+        m = PL.wmap_conv_dgrad_s1_part(wt.shape, g_t.c, c0, split)
+        probs.append(PL.conv_problem(g_t, 1, 3, 1, ops.pack_weight(wt, m), m, g_h))
+        halves.append(g_h)
+    ops.conv(probs)
+    return halves
+
+
+def _convT2_bwd(P, G, name, xin, g_y):
+    """Backward of _convT2 (ConvTranspose2d(k=2, s=2, p=0), weight (I, O, 2, 2)): g_y [N, 2h, 2w, O] (no border
+    needed: the four taps tile the output) -> the gradient of xin [N, h, w, I]; weight and bias gradients into G"""
+    wt = P[name + ".weight"]
+    G.wgrad(PL.wgrad_convT(xin, g_y, 2, 0, wt.shape[0]), PL.wmap_wgrad(wt.shape, True, g_y.c, 2), name + ".weight",
+            (xin, g_y))
+    ops.channel_sum(g_y, wt.shape[1], G.get(name + ".bias"), G.acc)
+    g_x = Buf.empty(xin.n, xin.h, xin.w, wt.shape[0], 0, g_y.t.device)
+    m = PL.wmap_convT_dgrad(wt.shape, g_y.c)
+    ops.conv([PL.conv_problem(g_y, 0, 2, 2, ops.pack_weight(wt, m), m, g_x)])     # one GEMM, K = 4 O
+    return g_x
+
+
+EVAL_BACKWARD = ("floodgan: the segmentation UNet's backward runs through the batch statistics of training-mode "
+                 "BatchNorm (models/segmentation_model.py:259 trains under model.train()); a backward in .eval() mode "
+                 "is not implemented")
+
+
+def unet_backward(P, S, g_logits, grads_into=None, choices=None):
+    """Explicit backward of unet_logits(save=True) through training-mode BatchNorm.  g_logits: Buf [N, H, W, >= 4],
+    dL/d(logits) in channel 0.  Returns {parameter name: gradient} (written into grads_into[name] when given).  The
+    gradient of the input image is not computed.  choices (dict, test instrumentation): receives
+    {"pool<k>": uint8 NCHW} -- the window position each max-pool gradient went to."""
+    if not S["training"]:
+        raise RuntimeError(EVAL_BACKWARD)
+    N, H, W = S["N"], S["H"], S["W"]
+    if (g_logits.n, g_logits.h, g_logits.w) != (N, H, W):
+        raise RuntimeError(f"unet_backward: logits gradient {g_logits.n}x{g_logits.h}x{g_logits.w} for a saved "
+                           f"forward of {N}x{H}x{W}")
+    dev = g_logits.t.device
+    G = X._Grads(P, grads_into, device=dev)
+    enc, dec, head = layer_names()
+    # ---- OutConv 1x1, 64 -> 1 (weight + bias, then the input gradient)
+    y = S["dec"][3]["out"]
+    ops.conv1x1_wgrad(g_logits, y, 1, G.get(head + ".weight"), G.get(head + ".bias"), G.acc)
+    g = Buf.empty(N, H, W, 64, 0, dev)
+    ops.conv1x1_dgrad(g_logits, P[head + ".weight"], 1, g)
+    # ---- decoder, up4 .. up1
+    g_skip = {}
+    for i in reversed(range(4)):
+        k = 3 - i
+        up, names = dec[i]
+        D = S["dec"][i]
+        g_skip[k], g_up = _double_conv_bwd(P, G, names, D, g, split=ENC[k])
+        g = _convT2_bwd(P, G, up, D["xin"], g_up)
+    # ---- encoder, down4 .. inc
+    for k in range(4, -1, -1):
+        E = S["enc"][k]
+        if k == 4:
+            gA, gB = g, None
+        else:
+            src = E["out"]
+            gA = Buf.empty(N, src.h, src.w, src.c, 0, dev)
+            ch = None
+            if choices is not None:
+                ch = torch.empty(N, src.h // 2, src.w // 2, src.c, dtype=torch.uint8, device=dev)
+                choices[f"pool{k}"] = ch.permute(0, 3, 1, 2)
+            ops.maxpool2_bwd(src, g, gA, ch)
+            gB = g_skip.pop(k)
+        g = _double_conv_bwd(P, G, enc[k], E, gA, gB, need_input=k > 0)
+    G.join()
+    return G.out
+
+
+def unet_decisions(S):
+    """The forward's ReLU decisions in a saved forward, keyed "<BatchNorm name>" -> NCHW bool on the host (test
+    instrumentation: tests/seg_train_oracle.py teacher-forces them; the max-pool choices come from
+    unet_backward(choices=...), which makes them)"""
+    enc, dec, _ = layer_names()
+    out = {}
+    for names, D in list(zip(enc, S["enc"])) + [(n, D) for (_, n), D in zip(dec, S["dec"])]:
+        out[names[1]] = X._decided(D["a"])
+        out[names[3]] = X._decided(D["out"])
+    return out
 
 
 def unit_image(x, buf=None, nchw=True):
@@ -126,18 +266,42 @@ def _sd_keys(module):
 
 
 class _UNetFn(torch.autograd.Function):
+    """forward: the native executor; activations are saved only when a gradient can be computed from them: the
+    caller's grad mode on (autograd runs forward with grad mode off, so it arrives as `save`), a parameter needing
+    one, and the module in train() mode.  backward: unet_backward on the parameters autograd saved (an in-place
+    update of one between forward and backward is caught by its version check)"""
+
     @staticmethod
-    def forward(ctx, module, x, *params):
-        P = dict(zip(_sd_keys(module), params))
+    def forward(ctx, module, save, x, *params):
+        keys = _sd_keys(module)
+        P = dict(zip(keys, params))
         B = dict(module.named_buffers())
         _, X0 = unit_image_passthrough(x)
-        logits = unet_logits(P, B, X0, module.training)
+        wants_x, wants_p = bool(save and ctx.needs_input_grad[2]), bool(save and any(ctx.needs_input_grad[3:]))
+        if wants_x:
+            raise RuntimeError("floodgan: the segmentation UNet does not compute the gradient of its input image "
+                               "(pass an input with requires_grad=False)")
+        ctx.S, ctx.eval_mode = None, wants_p and not module.training
+        if wants_p and module.training:
+            logits, ctx.S = unet_logits(P, B, X0, True, save=True)
+            ctx.keys = keys
+            ctx.save_for_backward(*params)
+        else:
+            logits = unet_logits(P, B, X0, module.training)
         return logits.interior()[..., :1].permute(0, 3, 1, 2).contiguous()
 
     @staticmethod
     def backward(ctx, g):
-        raise RuntimeError("floodgan: the segmentation UNet is evaluation-only (SURVEY.md §8(f) row 4); training it "
-                           "(models/segmentation_model.py:250-277) is out of scope")
+        if ctx.eval_mode:
+            raise RuntimeError(EVAL_BACKWARD)
+        if ctx.S is None:
+            raise RuntimeError("floodgan: segmentation UNet backward without a saved forward")
+        P, S = dict(zip(ctx.keys, ctx.saved_tensors)), ctx.S
+        ctx.S = None                                     # (a second backward through the same graph is an error)
+        g_logits = Buf.empty(S["N"], S["H"], S["W"], 4, 0, g.device)
+        ops.pack_input(g, 1, None, 0, g_logits, 0, S["N"], FG_PAD_ZERO)
+        grads = unet_backward(P, S, g_logits)
+        return (None, None, None) + tuple(grads[k] if need else None for k, need in zip(P, ctx.needs_input_grad[3:]))
 
 
 def unit_image_passthrough(x):
@@ -208,7 +372,8 @@ class OutConv(nn.Module):
 
 class UNet(nn.Module):
     """models/model_architectures.py:508-538 -- same modules, registration order and state_dict keys;
-    forward = the native executor (logits [N, 1, H, W]); evaluation-only."""
+    forward = the native executor (logits [N, 1, H, W]); in train() mode it trains under stock loss.backward() and
+    any torch optimizer (no gradient of the input image; no backward in eval() mode)."""
 
     def __init__(self, n_channels=3, n_classes=1, bilinear=False):
         super().__init__()
@@ -232,7 +397,7 @@ class UNet(nn.Module):
 
     def forward(self, x):
         self._check()
-        return _UNetFn.apply(self, x, *[p for _, p in self.named_parameters()])
+        return _UNetFn.apply(self, torch.is_grad_enabled(), x, *[p for _, p in self.named_parameters()])
 
     def logits_from_buf(self, X0):
         """logits Buf from a prepared input Buf (the evaluation path: unit_image writes it directly)"""
@@ -255,24 +420,196 @@ def initialise_weights(m):
         nn.init.constant_(m.bias.data, 0.0)
 
 
-class SegmentationModel:
-    """models/segmentation_model.py:19-72, the evaluation side: the UNet, initialised as the reference
-    does (no reseeding: it draws from the global generator), optionally loaded from a checkpoint
-    ({"model": state_dict, "current_epoch", "num_epochs", "all_losses", "all_accuracies"}, read with
-    weights_only=True).  Training the segmentation model (train_model) is out of scope."""
+class SegStep:
+    """One segmentation training iteration (models/segmentation_model.py:261-274) on device tensors x [N, 3, H, W]
+    and true_mask [N, 1, H, W]: native forward, BCE-with-logits with the accuracy count (fg_bce_logits), explicit
+    backward into the parameters' .grad, optimizer step.  Returns one 16-byte device tensor holding (loss, number
+    of correct mask elements): a single copy brings both to the host (SegStep.read)."""
 
-    def __init__(self, data_path=None, pretrained_model_path=None, train=False, device="cuda", seed=47):
-        if train:
-            raise NotImplementedError("floodgan: segmentation-model training is out of scope (SURVEY.md §8(f) row 4 "
-                                      "is evaluation inference)")
+    def __init__(self, model, optimizer):
+        self.model, self.opt = model, optimizer
+        self.P = dict(model.named_parameters())
+        # test instrumentation: when True, each call stores its ReLU decisions, max-pool choices and logits in
+        # self.decisions ({"relu": {...}, "pool": {...}, "logits": NCHW host tensor})
+        self.record_decisions = False
+        self.decisions = None
+
+    def __call__(self, x, true_mask):
+        self.model._check()
+        require_device(true_mask, "segmentation target")
+        N, _, H, W = x.shape
+        dev = x.device
+        _, X0 = unit_image_passthrough(x)
+        logits, S = unet_logits(self.P, dict(self.model.named_buffers()), X0, self.model.training, save=True)
+        res = torch.empty(2, dtype=torch.int64, device=dev)         # [0]: the fp32 loss in its low half, [1]: count
+        g = Buf.empty(N, H, W, 4, 0, dev)
+        ops.bce_logits(logits, true_mask.contiguous(), 1.0 / (N * H * W), g, res[:1].view(torch.float32), res[1:])
+        for p in self.P.values():                                   # optimizer.zero_grad(): every gradient is
+            if p.grad is None:                                      # overwritten below
+                p.grad = torch.empty_like(p)
+        choices = {} if self.record_decisions else None
+        if self.record_decisions:
+            self.decisions = dict(relu=unet_decisions(S), pool=choices,
+                                  logits=logits.interior()[..., :1].permute(0, 3, 1, 2).cpu())
+        unet_backward(self.P, S, g, grads_into={k: p.grad for k, p in self.P.items()}, choices=choices)
+        del S
+        if choices:
+            self.decisions["pool"] = {k: v.cpu() for k, v in choices.items()}
+        self.opt.step()
+        return res
+
+    @staticmethod
+    def read(res, numel):
+        """(loss, accuracy) on the host from a step's result: one device-to-host copy"""
+        host = res.cpu()
+        return float(host[:1].view(torch.float32)[0]), int(host[1]) / numel
+
+
+class SegmentationModel:
+    """models/segmentation_model.py:19-177, 244-277: the UNet, initialised as the reference does (no reseeding: it
+    draws from the global generator), optionally loaded from a checkpoint ({"model": state_dict, "current_epoch",
+    "num_epochs", "all_losses", "all_accuracies"}, read with weights_only=True; the reference's checkpoints load
+    here and these load there).  train=True: BCE-with-logits (fg_bce_logits), FusedAdam(1e-4, (0.5, 0.999)), the
+    LambdaLR of lambda_rule, starting_epoch resumed from the checkpoint; train_model() runs the fused SegStep.
+    The loaders come from floodgan.data.create_masks_dataset when data_path is given, or are assigned
+    (train_loader / val_loader / test_loader: iterables of (image, mask, names)).  Every keyword of the reference's
+    constructor is accepted (segment.py passes them all); the plots are out of scope: save_images_interval != 0 and
+    plot_mask_image raise."""
+
+    def __init__(self, data_path=None, pretrained_model_path=None, train=False, device="cuda", seed=47,
+                 dataset_subset="usa", num_epochs=100, train_on_all=False, save_model_interval=0, verbose=True,
+                 save_images_interval=0, plot_mask_image=None, use_test_data=False,
+                 csv_path="metadata/masks_metadata.csv"):
+        if save_images_interval != 0 or plot_mask_image:
+            raise NotImplementedError("floodgan: the segmentation model's plots (save_images_interval != 0: "
+                                      "plot_sample_images / plot_loss; plot_mask_image) are out of scope; pass "
+                                      "save_images_interval=0 and plot_mask_image=None")
+        self.save_images_interval, self.use_test_data = 0, use_test_data
         self.data_path, self.pretrained_model_path, self.seed = data_path, pretrained_model_path, seed
-        self.current_epoch, self.num_epochs, self.all_losses, self.all_accuracies = 1, 100, [], []
+        self.dataset_subset, self.train_on_all, self.train = dataset_subset, train_on_all, train
+        self.save_model_interval, self.verbose, self.csv_path = save_model_interval, verbose, csv_path
+        self.device = device
+        self.starting_epoch = 1
+        self.current_epoch, self.num_epochs, self.all_losses, self.all_accuracies = 1, num_epochs, [], []
         self.model = UNet().apply(initialise_weights).to(device)
         if pretrained_model_path:
             saved = torch.load(pretrained_model_path, map_location="cpu", weights_only=True)
             self.current_epoch, self.num_epochs = saved["current_epoch"], saved["num_epochs"]
             self.model.load_state_dict(saved["model"])
             self.all_losses, self.all_accuracies = saved["all_losses"], saved["all_accuracies"]
+        self.train_loader = self.val_loader = self.test_loader = None
+        self._step = None
+        if train:
+            from torch.optim import lr_scheduler
+
+            from .optim import FusedAdam
+            self.starting_epoch = self.current_epoch
+            self.optimizer = FusedAdam(self.model.parameters(), lr=0.0001, betas=(0.5, 0.999))
+            self.scheduler = lr_scheduler.LambdaLR(self.optimizer, lr_lambda=self.lambda_rule)
+            if data_path is not None:
+                self.train_loader, self.val_loader, self.test_loader = self._loaders()
+
+    def _loaders(self):
+        from .data import create_masks_dataset
+        return create_masks_dataset(self.dataset_subset, self.data_path, self.train_on_all, csv_path=self.csv_path)
+
+    def lambda_rule(self, epoch):
+        """models/segmentation_model.py:86-92: constant for the first half of the epochs, then linear decay"""
+        return 1.0 - max(0, epoch + 1 - (self.num_epochs / 2)) / float((self.num_epochs / 2) + 1)
+
+    def create_path(self, save_type):
+        """models/segmentation_model.py:94-105"""
+        from datetime import datetime
+        ext = {"image": ".png", "figure": ".png", "model": ".pth.tar", "metric": ".csv"}[save_type]
+        now = str(datetime.now())[:-7].replace(" ", "-").replace(":", "-")
+        return (f"{self.data_path}/{save_type}s/"
+                f"SegmentationModel_epoch{self.current_epoch if self.train else self.current_epoch - 1}_"
+                f"{self.dataset_subset}Data_date{now}{ext}")
+
+    @property
+    def step_fn(self):
+        if self._step is None:
+            self._step = SegStep(self.model, self.optimizer)
+        return self._step
+
+    def train_model(self):
+        """models/segmentation_model.py:250-277 on the fused device step; loss and accuracy reach the host once
+        per batch"""
+        if not self.train:
+            raise RuntimeError("SegmentationModel.train_model needs train=True")
+        if self.train_loader is None:
+            raise RuntimeError("no training data: pass data_path (floodgan.data.create_masks_dataset, as "
+                               "models/segmentation_model.py:69-71) or assign train_loader (an iterable of "
+                               "(image, mask, names))")
+        for epoch in range(self.starting_epoch, self.num_epochs + 1):
+            t0 = time.time()
+            losses, accuracies = [], []
+            self.model.train()
+            for input_image, true_mask, _ in self.train_loader:
+                input_image = input_image.to(self.device, non_blocking=True)
+                true_mask = true_mask.to(self.device, non_blocking=True)
+                loss, acc = SegStep.read(self.step_fn(input_image, true_mask), true_mask.numel())
+                losses.append(loss)
+                accuracies.append(acc)
+            self.scheduler.step()
+            self.save_results(epoch, losses, accuracies, t0)
+
+    def checkpoint(self, epoch):
+        """the reference's checkpoint dict (models/segmentation_model.py:122-127)"""
+        return {"current_epoch": epoch + 1, "num_epochs": self.num_epochs, "model": self.model.state_dict(),
+                "all_losses": self.all_losses, "all_accuracies": self.all_accuracies}
+
+    def save_results(self, epoch, losses, accuracies, epoch_start_time):
+        """models/segmentation_model.py:107-134 (per-epoch means + checkpoint; plots are out of scope)"""
+        import os
+        self.current_epoch = epoch
+        self.all_losses.append(float(np.mean(losses)))
+        self.all_accuracies.append(float(np.mean(accuracies)))
+        if self.verbose:
+            print(f"Epoch {epoch} ({time.time() - epoch_start_time:.2f} seconds) | Loss = {self.all_losses[-1]:.2f} | "
+                  f"Accuracy = {self.all_accuracies[-1]:.2f}")
+        if self.save_model_interval != 0 and epoch % self.save_model_interval == 0:
+            path = self.create_path("model")
+            if self.verbose:
+                print(f"Saving flood segmentation model to {path}")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            torch.save(self.checkpoint(epoch), path)
+            return path
+        return None
+
+    def calculate_metrics(self, use_test_data=False):
+        """models/segmentation_model.py:136-177: the binary mask metrics of the model's flood masks against the
+        true masks (t > 0.5) over the validation / test loader, accumulated on the device (MaskConfusion: a true
+        mask t > 0.5 is the logit t - 0.5).  Returns the one-row DataFrame the reference prints (and writes it
+        under data_path/metrics/ when data_path is set)."""
+        import os
+
+        import pandas as pd
+
+        from .evaluate import MaskConfusion
+        val_loader, test_loader = self.val_loader, self.test_loader
+        if val_loader is None and test_loader is None and self.data_path is not None:
+            _, val_loader, test_loader = self._loaders()
+        loader = test_loader if use_test_data else val_loader
+        if loader is None:
+            raise RuntimeError("no evaluation data: pass data_path or assign val_loader / test_loader")
+        conf = MaskConfusion(self.device)
+        for input_image, true_mask, _ in loader:
+            x = input_image.to(self.device)
+            t = true_mask.to(self.device)
+            N, _, H, W = x.shape
+            pred = self.model.logits_from_buf(unit_image_passthrough(x)[1])
+            true = Buf.zeros(N, H, W, 4, 0, x.device)
+            true.interior()[..., 0] = t[:, 0] - 0.5
+            conf.update(pred, true)
+        df = pd.DataFrame([(k, v) for k, v in conf.compute().items()]).set_index(0).transpose()
+        if self.verbose:
+            print(df)
+        if self.data_path:
+            path = self.create_path("metric")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            df.to_csv(path)
+        return df
 
     @staticmethod
     def tensor_to_mask(tensor, predicted=True):

@@ -578,6 +578,22 @@ int fg_bernoulli_mt(const unsigned* state, long long first, long long elements, 
                     unsigned* final_state, unsigned* work, hipStream_t stream);
 /* nn.MaxPool2d(2) over NHWC interiors (floor output size). */
 int fg_maxpool2(fg_view src, fg_view dst, hipStream_t stream);
+/* Gradient of fg_maxpool2: each pooled element's gradient (g_pooled, src.h / 2 x src.w / 2) goes to the FIRST
+ * maximum of its 2x2 window of the saved source in the scan order (0,0), (0,1), (1,0), (1,1) -- ATen's rule: a
+ * later element wins only when strictly greater (or NaN), so an all-zero post-ReLU window routes to (0,0).  All
+ * four positions of g_src's interior are written (the non-maxima, and an odd last row / column, as zero): no
+ * pre-zeroing, no dependence on execution order.  choice (optional, 4-byte aligned): the chosen position 0..3 per
+ * pooled element as bytes in NHWC order [n, src.h / 2, src.w / 2, c_alloc] (test instrumentation). */
+int fg_maxpool2_bwd(fg_view src, fg_view g_pooled, fg_view g_src, unsigned char* choice, hipStream_t stream);
+/* nn.BCEWithLogitsLoss() (mean) of channel 0 of `logits` against a contiguous [N, 1, H, W] target in [0, 1], in
+ * one pass: loss[0] = mean(max(z, 0) - z t + log1p(exp(-|z|))); grad (a whole buffer, not a channel slice)
+ * channel 0 = (sigmoid(z) - t) * gscale, its other channels and its border zero; correct[0] (optional) = the
+ * number of elements with (sigmoid(z) > 0.5) == (t > 0.5), sigmoid(z) > 0.5 decided as z > 0
+ * (models/segmentation_model.py:273).  Deterministic: fp32 per thread, fp64 across threads and blocks, no
+ * floating-point atomics.  work: fg_bce_logits_workspace_doubles() doubles. */
+long long fg_bce_logits_workspace_doubles(void);
+int fg_bce_logits(fg_view logits, const float* target, float gscale, fg_view grad, float* loss, long long* correct,
+                  double* work, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------- */
 /* evaluation metrics (models/model.py:363-422, models/group.py:114-221) */
