@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 import seg_train_oracle as SO
 from test_gpu_northstar import KINK, _update_agreement
-from test_gpu_parity import DEV, NTOL, buf_from, nchw, nrel
+from test_gpu_parity import DEV, KTOL, MATHS, NTOL, buf_from, conv_math, nchw, nrel  # noqa: F401  (conv_math: fixture)
 from test_seg_train_oracle_golden import EPOCHS, NUM_EPOCHS, checksum, load_gold, synth_batches
 
 pytestmark = pytest.mark.gpu
@@ -76,6 +76,57 @@ def test_bce_logits_vs_fp64():
     assert float(border.abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("N,H,W,pad", [(1, 516, 512, 0), (2, 37, 45, 1)])
+def test_bce_logits_grid_stride_and_second_quad(N, H, W, pad):
+    """fg_bce_logits where its loops go round again: 516 x 512 is 264192 pixels, more than the 1024 blocks x 256
+    threads the launch is capped at, so the grid-stride loop takes a second iteration for the last 2048 of them (the
+    workload's 1024^2 takes four); the gradient buffer has 8 channels, so the channel-quad loop writes a second
+    quad.  The second shape has a border on both buffers.  Same assertions as test_bce_logits_vs_fp64"""
+    from floodgan import ops
+    from floodgan.plans import Buf
+    g = torch.Generator().manual_seed(12 + pad)
+    z = torch.randn((N, 1, H, W), generator=g) * 3
+    special = [0.0, 1e-3, -1e-3, 20.0, -20.0, 90.0, -90.0]
+    tv = torch.tensor([0.0, 1.0, 0.3])
+    t = tv[torch.randint(0, 3, (N, 1, H, W), generator=g)]
+    for i, s in enumerate(special):                      # every special logit against every target value, at the
+        for j in range(3):                               # start of the pixel range and inside its last 2048
+            for y0 in (3, H - len(special)):
+                z[i % N, 0, y0 + i, 5 + j] = s
+                t[i % N, 0, y0 + i, 5 + j] = tv[j]
+    if pad == 0:
+        assert N * H * W > 1024 * 256
+    logits = buf_from(z, pad, "constant", 4)
+    logits.nhwc()[..., 1:] = 7.0                         # only channel 0 is read
+    gscale = 1.0 / z.numel()
+    td = t.to(DEV)
+    runs = []
+    for _ in range(2):
+        grad = Buf(torch.full(((N * (H + 2 * pad) * (W + 2 * pad)) * 8,), float("nan"), device=DEV), N, H, W, 8, pad)
+        res = torch.zeros(2, dtype=torch.int64, device=DEV)
+        ops.bce_logits(logits, td, gscale, grad, res[:1].view(torch.float32), res[1:])
+        runs.append((grad.nhwc().cpu(), res.cpu()))
+    (gr, res), (gr2, res2) = runs
+    assert torch.equal(gr, gr2) and torch.equal(res, res2)              # deterministic: bit-identical
+    z64, t64 = z.double(), t.double()
+    loss_ref = float(F.binary_cross_entropy_with_logits(z64, t64))
+    g_ref = (torch.sigmoid(z64) - t64) * gscale
+    correct_ref = int(((torch.sigmoid(z64) > 0.5) == (t64 > 0.5)).sum())
+    loss = float(res[:1].view(torch.float32)[0])
+    inner = gr[:, pad:pad + H, pad:pad + W]
+    e_loss, e_grad = abs(loss - loss_ref) / loss_ref, nrel(inner[..., 0], g_ref[:, 0])
+    print(f"bce_logits {N}x{H}x{W} pad {pad}: loss {loss} vs {loss_ref} (rel {e_loss:.2e}); gradient nrel "
+          f"{e_grad:.2e}; correct {int(res[1])} vs {correct_ref}")
+    assert e_loss < 1e-6
+    assert e_grad < 1e-6
+    assert int(res[1]) == correct_ref
+    assert not torch.isnan(gr).any()                                    # every pixel of the padded extent written
+    assert float(gr[..., 1:].abs().max()) == 0.0                       # padded channels, both quads
+    border = gr.clone()
+    border[:, pad:pad + H, pad:pad + W] = 0
+    assert float(border.abs().max()) == 0.0
+
+
 def _pool_source(N, C, H, W, seed):
     """post-ReLU values with every kind of window: all zero, four and two equal positive maxima, and a strict
     maximum in each of the four positions (in every channel and image), random post-ReLU windows elsewhere"""
@@ -115,6 +166,121 @@ def test_maxpool2_bwd_bit_exact(C):
     pooled = Buf.zeros(N, H // 2, W // 2, C, 0, DEV)
     ops.maxpool2(src, pooled)
     assert torch.equal(nchw(pooled), F.max_pool2d(x, 2))
+
+
+def _maxpool2_bwd_case(x, spad, dpad, gpad, seed):
+    """fg_maxpool2_bwd of the source x (NCHW, any H, W >= 2) into a NaN-filled destination, bit-exact against
+    autograd's max_pool2d gradient (zero in an odd last row / column) and against SO.first_max"""
+    from floodgan import ops
+    from floodgan.plans import Buf
+    N, C, H, W = x.shape
+    gy = torch.randn((N, C, H // 2, W // 2), generator=torch.Generator().manual_seed(seed))
+    xr = x.clone().requires_grad_(True)
+    (ref,) = torch.autograd.grad(F.max_pool2d(xr, 2), xr, gy)
+    src, gp = buf_from(x, spad, "constant"), buf_from(gy, gpad, "constant")
+    dst = Buf(torch.full((N * (H + 2 * dpad) * (W + 2 * dpad) * C,), float("nan"), device=DEV), N, H, W, C, dpad)
+    choice = torch.full((N, H // 2, W // 2, C), 9, dtype=torch.uint8, device=DEV)
+    ops.maxpool2_bwd(src, gp, dst, choice)
+    got = nchw(dst)
+    assert torch.equal(got, ref)                         # every interior element written, bit-exact
+    if H % 2:
+        assert float(got[:, :, -1].abs().max()) == 0.0   # outside every window: exactly zero, not left NaN
+    if W % 2:
+        assert float(got[:, :, :, -1].abs().max()) == 0.0
+    full = dst.nhwc().cpu()
+    full[:, dpad:dpad + H, dpad:dpad + W] = float("nan")
+    assert bool(torch.isnan(full).all())                 # the destination's border is not touched
+    first = SO.first_max(x[:, :, :H // 2 * 2, :W // 2 * 2])
+    assert torch.equal(choice.permute(0, 3, 1, 2).cpu().long(), first)
+    return first
+
+
+@pytest.mark.parametrize("H,W,spad,dpad", [(7, 9, 0, 1), (7, 9, 1, 0), (3, 2, 0, 1), (3, 2, 1, 0)])
+def test_maxpool2_bwd_odd_sizes_and_pads(H, W, spad, dpad):
+    """the kernel's !full branch: an odd last row / column of the source lies outside every pooled window and its
+    gradient is written as zero; source and destination with different borders (their strides differ)"""
+    if W >= 8:
+        x = _pool_source(2, 8, H, W, 7)                  # its ties and strict maxima sit in rows 0..3, columns 0..7
+    else:
+        x = torch.relu(torch.randn((2, 8, H, W), generator=torch.Generator().manual_seed(8)))
+        x[:, :4, 0:2, 0:2] = 1.5                         # a four-way tie in half of the channels: position 0 wins
+    first = _maxpool2_bwd_case(x, spad, dpad, 1 - dpad, 9)
+    if W >= 8:
+        assert [int(first[0, 0, 1, p]) for p in range(4)] == [0, 1, 2, 3]
+    else:
+        assert int(first[0, 0, 0, 0]) == 0
+
+
+def test_maxpool2_bwd_grid_stride():
+    """1 x 256 x 258 x 256: 129 * 128 * 64 = 1,056,768 (window, channel quad) items, more than the 4096 blocks x 256
+    threads the launch is capped at -- the grid-stride loop takes a second iteration (the workload's 1024^2 level-1
+    pool has 4.2 M items)"""
+    N, C, H, W = 1, 256, 258, 256
+    assert N * (H // 2) * (W // 2) * (C // 4) > 4096 * 256
+    x = _pool_source(N, C, H, W, 10)
+    x[:, :, -2:] = x[:, :, 0:2]                          # the same ties in the windows of the second iteration
+    first = _maxpool2_bwd_case(x, 0, 0, 0, 11)
+    assert int(first[0, 0, 0, 0]) == 0 and int(first[0, 0, 0, 1]) == 0 and int(first[0, 0, 0, 2]) == 1
+    assert torch.equal(first[:, :, -1], first[:, :, 0])
+
+
+@pytest.mark.parametrize("N,H,W", [(2, 5, 7), (1, 96, 96)])
+def test_conv1x1_head_one_output_in_four_channels(N, H, W):
+    """fg_conv1x1_dgrad / fg_conv1x1_wgrad as the segmentation head calls them: n_out = 1 with a 4-channel gradient
+    buffer (test_conv1x1_head has 16 channels and n_out 3 .. 16).  Channels 1..3 of the gradient are NaN: never
+    read; the weight gradient written, then accumulated"""
+    from floodgan import ops
+    from floodgan.plans import Buf
+    g = torch.Generator().manual_seed(33)
+    x = torch.randn((N, 64, H, W), dtype=torch.float64, generator=g)
+    w = (torch.randn((1, 64, 1, 1), dtype=torch.float64, generator=g) * 0.1).requires_grad_(True)
+    b = torch.randn((1,), dtype=torch.float64, generator=g).requires_grad_(True)
+    xr = x.clone().requires_grad_(True)
+    y = F.conv2d(xr, w, b)
+    gy = torch.randn(y.shape, dtype=torch.float64, generator=g)
+    gx_ref, gw_ref, gb_ref = torch.autograd.grad(y, (xr, w, b), gy)
+    X = buf_from(x, 0, "constant")
+    wd = w.detach().float().to(DEV)
+    GY = buf_from(gy, 0, "constant", c_alloc=4)
+    GY.nhwc()[..., 1:] = float("nan")
+    GX = Buf(torch.full((N * H * W * 64,), float("nan"), device=DEV), N, H, W, 64, 0)
+    ops.conv1x1_dgrad(GY, wd, 1, GX)
+    dw = torch.full(w.shape, 3.0, device=DEV)
+    db = torch.full((1,), -2.0, device=DEV)
+    ops.conv1x1_wgrad(GY, X, 1, dw, db)
+    torch.cuda.synchronize()
+    e = dict(dgrad=nrel(nchw(GX), gx_ref), wgrad=nrel(dw, gw_ref), bgrad=nrel(db, gb_ref))
+    ops.conv1x1_wgrad(GY, X, 1, dw, db, accumulate=True)
+    torch.cuda.synchronize()
+    e.update(wgrad_acc=nrel(dw, 2 * gw_ref), bgrad_acc=nrel(db, 2 * gb_ref))
+    print(f"conv1x1 head n_out 1 in 4 channels, {N}x{H}x{W}:", e)
+    assert max(e.values()) < KTOL, e
+
+
+@pytest.mark.parametrize("conv_math", MATHS, indirect=True)
+def test_head_forward_one_output_in_four_channels(conv_math, report):
+    """the OutConv forward as unet_logits runs it: a 1x1 conv with one output on the conv engine into the 4-channel
+    logits buffer, in every conv math; channels 1..3 are not written"""
+    from floodgan import ops, pix2pix as P2P
+    from floodgan.plans import Buf
+    N, H, W = 2, 6, 10
+    g = torch.Generator().manual_seed(34)
+    x = torch.randn((N, 64, H, W), dtype=torch.float64, generator=g)
+    w = torch.randn((1, 64, 1, 1), dtype=torch.float64, generator=g) * 0.1
+    b = torch.randn((1,), dtype=torch.float64, generator=g)
+    ref = F.conv2d(x, w, b)
+    P = {"outc.conv.weight": w.float().to(DEV), "outc.conv.bias": b.float().to(DEV)}
+    logits = Buf(torch.full((N * H * W * 4,), float("nan"), device=DEV), N, H, W, 4, 0)
+    P2P._conv_nb(P, "outc.conv", buf_from(x, 0, "constant"), 0, 1, 1, logits)
+    kernel = ops.LAST_CONV_KERNEL
+    out = logits.nhwc().cpu()
+    e = nrel(out[..., 0], ref[:, 0])
+    print(f"segmentation head forward [{conv_math}]: nrel {e:.2e} ({kernel})")
+    report("seg_head_forward", math=conv_math, nrel=e, kernel=kernel)
+    # one output: below the pipelined kernel's 33 (fgc::f3_config), so f16x3 runs its register-staged kernel
+    assert kernel == {"fp32": "conv_fwd"}.get(conv_math, "conv_fwd_x6")
+    assert e < KTOL
+    assert bool(torch.isnan(out[..., 1:]).all())
 
 
 @pytest.mark.parametrize("shape", [(2, 128, 6, 10), (1, 1024, 2, 2)])

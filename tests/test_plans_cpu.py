@@ -1,14 +1,17 @@
 """CPU check of the convolution plans (floodgan/plans.py): a numpy emulation of exactly the
 addressing the HIP engine performs (fg_conv_problem / fg_wgrad_problem / fg_weight_map,
 include/floodgan.h) must reproduce torch's conv2d / conv_transpose2d forward, input and weight
-gradients for every geometry of the PairedAttention path."""
+gradients for every geometry of the PairedAttention path and for the forms the two U-Nets add: the segmentation
+U-Net's 3x3 convs over a 3-in-4-channel image, its ConvTranspose2d(2, 2, 0) into one half of a cat buffer and the
+input gradient split over the cat's halves; Pix2Pix's ConvTranspose2d(4, 2, 1), down to 1 x 1 inputs and 3 outputs
+in a 4-channel buffer."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from floodgan import plans as PL
-from floodgan.plans import Buf
+from floodgan.plans import Buf, Slice
 
 
 # ---------------- emulator ----------------
@@ -315,3 +318,128 @@ def test_quad_map_and_problem():
                     yv[base + o + p["q_yoff"][q]] = out[n]
     got = Y.interior().permute(0, 3, 1, 2)
     assert float((got - ref).abs().max()) < 1e-10
+
+
+# ---------------- the U-Nets' forms ----------------
+
+SENTINEL = 7.0      # what a plan must leave alone
+
+
+@pytest.mark.parametrize("N,H,W", [(1, 2, 2), (2, 6, 10)])
+def test_conv3_rgb_in_four_channels_plan(N, H, W):
+    """the segmentation U-Net's first conv (3x3, stride 1, zero pad 1) over a 3-channel image held in 4 channels:
+    forward, weight gradient (the padding channel's slab columns dropped) and input gradient (3 outputs into a
+    4-channel buffer, channel 3 untouched)"""
+    cin, cout = 3, 8
+    x = torch.randn(N, cin, H, W, requires_grad=True)
+    w = torch.randn(cout, cin, 3, 3, requires_grad=True)
+    y = F.conv2d(x, w, padding=1)
+    gy = torch.randn_like(y)
+    gx_ref, gw_ref = torch.autograd.grad(y, (x, w), gy)
+    X = to_buf(x.detach(), 1, "constant", 4)
+    m = PL.wmap_conv_fwd(w.shape, X.c)
+    assert (m["c"], m["c_valid"], m["jp"]) == (4, 3, 16)
+    Y = Buf(torch.zeros(N * H * W * cout), N, H, W, cout, 0)
+    prob = PL.conv_problem(X, 1, 3, 1, emu_pack(w.detach(), m), m, Y)
+    assert prob["j_valid"] == 12 and prob["jp"] == 16
+    emu_conv(prob)
+    assert close(from_buf(Y), y.detach())
+    slab = emu_wgrad(PL.wgrad_conv(to_buf(gy, 0, "constant"), X, 1, 3, 1, cout))
+    dw = torch.zeros(w.shape)
+    emu_reduce(slab, PL.wmap_wgrad(w.shape, True, X.c, 3), dw)
+    assert close(dw, gw_ref)
+    G = to_buf(gy, 1, "constant")
+    md = PL.wmap_conv_dgrad_s1(w.shape, G.c)
+    GX = Buf(torch.full((N * H * W * 4,), SENTINEL), N, H, W, 4, 0)
+    emu_conv(PL.conv_problem(G, 1, 3, 1, emu_pack(w.detach(), md), md, GX))
+    assert close(from_buf(GX, 3), gx_ref)
+    assert bool((GX.interior()[..., 3] == SENTINEL).all())
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (3, 5), (2, 4)])
+@pytest.mark.parametrize("k,p", [(2, 0), (4, 1)])
+def test_convT_s2_unet_plans(k, p, H, W):
+    """ConvTranspose2d(k=2, s=2, p=0) (segmentation Up) and ConvTranspose2d(k=4, s=2, p=1) (Pix2Pix up convs):
+    the forward with bias as four phases into the second half of a 2c-channel cat buffer (the first half and the
+    border untouched), the weight gradient and the input gradient, on H != W and 1 x 1 inputs"""
+    N, cin, c = 2, 8, 4
+    x = torch.randn(N, cin, H, W, requires_grad=True)
+    w = torch.randn(cin, c, k, k, requires_grad=True)
+    b = torch.randn(c)
+    y = F.conv_transpose2d(x, w, b, stride=2, padding=p)
+    assert y.shape[-2:] == (2 * H, 2 * W)
+    gy = torch.randn_like(y)
+    gx_ref, gw_ref = torch.autograd.grad(y, (x, w), gy)
+    X = to_buf(x.detach(), 1, "constant")
+    wide = Buf(torch.full((N * (2 * H + 2) * (2 * W + 2) * 2 * c,), SENTINEL), N, 2 * H, 2 * W, 2 * c, 1)
+    maps = PL.phase_maps(w.shape, k, p, X.c)
+    wps = [emu_pack(w.detach(), m) for m, _, _ in maps]
+    for prob in PL.phase_problems(X, w.shape, k, p, Slice(wide, c, c), wps, maps, bias=b):
+        assert prob["kh"] == k // 2 and prob["syb"] == 2 * 2 * c
+        emu_conv(prob)
+    assert close(wide.interior()[..., c:].permute(0, 3, 1, 2), y.detach())
+    rest = wide.nhwc().clone()
+    rest[:, 1:-1, 1:-1, c:] = SENTINEL
+    assert bool((rest == SENTINEL).all())
+    # weight gradient: P = the transposed conv's input, the output gradient gathered with its zero border p
+    GY = to_buf(gy, p, "constant")
+    slab = emu_wgrad(PL.wgrad_convT(X, GY, k, p, cin))
+    dw = torch.zeros(w.shape)
+    emu_reduce(slab, PL.wmap_wgrad(w.shape, True, GY.c, k), dw)
+    assert close(dw, gw_ref)
+    # input gradient: one stride-2 conv of the output gradient, K = k * k * c
+    md = PL.wmap_convT_dgrad(w.shape, GY.c)
+    GX = Buf(torch.zeros(N * H * W * cin), N, H, W, cin, 0)
+    emu_conv(PL.conv_problem(GY, p, k, 2, emu_pack(w.detach(), md), md, GX))
+    assert close(from_buf(GX), gx_ref)
+
+
+@pytest.mark.parametrize("N,H,W", [(1, 2, 2), (2, 6, 10)])
+def test_conv_dgrad_s1_part_plan(N, H, W):
+    """the input gradient of a 3x3 conv over a cat buffer as its two channel halves (n_base 0 and c), each against
+    the matching channels of the whole gradient"""
+    c, cout = 4, 6
+    x = torch.randn(N, 2 * c, H, W, requires_grad=True)
+    w = torch.randn(cout, 2 * c, 3, 3)
+    y = F.conv2d(x, w, padding=1)
+    gy = torch.randn_like(y)
+    (ref,) = torch.autograd.grad(y, x, gy)
+    G = to_buf(gy, 1, "constant")
+    for c0 in (0, c):
+        m = PL.wmap_conv_dgrad_s1_part(w.shape, G.c, c0, c)
+        assert (m["n_base"], m["n_out"]) == (c0, c)
+        Y = Buf(torch.zeros(N * H * W * c), N, H, W, c, 0)
+        emu_conv(PL.conv_problem(G, 1, 3, 1, emu_pack(w, m), m, Y))
+        assert close(from_buf(Y), ref[:, c0:c0 + c])
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (3, 5)])
+def test_convT4_three_outputs_in_four_channels_plan(H, W):
+    """Pix2Pix's outermost up conv: ConvTranspose2d(k=4, s=2, p=1) with 3 outputs into a 4-channel buffer (channel 3
+    untouched); its weight gradient gathers that 4-channel gradient (the padding channel's columns dropped) and its
+    input gradient is a stride-2 conv over it"""
+    N, cin = 2, 8
+    x = torch.randn(N, cin, H, W, requires_grad=True)
+    w = torch.randn(cin, 3, 4, 4, requires_grad=True)
+    b = torch.randn(3)
+    y = F.conv_transpose2d(x, w, b, stride=2, padding=1)
+    gy = torch.randn_like(y)
+    gx_ref, gw_ref = torch.autograd.grad(y, (x, w), gy)
+    X = to_buf(x.detach(), 1, "constant")
+    Y = Buf(torch.full((N * 4 * H * W * 4,), SENTINEL), N, 2 * H, 2 * W, 4, 0)
+    maps = PL.phase_maps(w.shape, 4, 1, X.c)
+    assert all(m["n_out"] == 3 for m, _, _ in maps)
+    for prob in PL.phase_problems(X, w.shape, 4, 1, Y, [emu_pack(w.detach(), m) for m, _, _ in maps], maps, bias=b):
+        emu_conv(prob)
+    assert close(from_buf(Y, 3), y.detach())
+    assert bool((Y.interior()[..., 3] == SENTINEL).all())
+    GY = to_buf(gy, 1, "constant", 4)
+    prob = PL.wgrad_convT(X, GY, 4, 1, cin)
+    assert prob["j_valid"] == 16
+    dw = torch.zeros(w.shape)
+    emu_reduce(emu_wgrad(prob), PL.wmap_wgrad(w.shape, True, GY.c, 4), dw)
+    assert close(dw, gw_ref)
+    md = PL.wmap_convT_dgrad(w.shape, GY.c)
+    GX = Buf(torch.zeros(N * H * W * cin), N, H, W, cin, 0)
+    emu_conv(PL.conv_problem(GY, 1, 4, 2, emu_pack(w.detach(), md), md, GX))
+    assert close(from_buf(GX), gx_ref)
