@@ -14,8 +14,10 @@ from .model_architectures import (AttentionGANBlock, AttentionGANDiscriminator, 
                                   PairedAttentionBlock, PairedAttentionDiscriminator, PairedAttentionGenerator,
                                   Pix2PixBlock, Pix2PixDiscriminator, Pix2PixGenerator)
 from .segmentation import UNet  # noqa: F401
+from .evaluate import LPIPS, load_lpips_weights  # noqa: F401
 
 __all__ = ["PairedAttentionGenerator", "PairedAttentionBlock", "PairedAttentionDiscriminator",
            "AttentionGANGenerator", "AttentionGANBlock", "AttentionGANDiscriminator",
            "CycleGANGenerator", "CycleGANBlock", "CycleGANDiscriminator",
-           "Pix2PixGenerator", "Pix2PixBlock", "Pix2PixDiscriminator", "UNet", "load_library"]
+           "Pix2PixGenerator", "Pix2PixBlock", "Pix2PixDiscriminator", "UNet", "load_library", "LPIPS",
+           "load_lpips_weights"]

@@ -200,6 +200,10 @@ SIGNATURES = {
     "fg_sq_err_workspace_doubles": [],
     "fg_sq_err_sum": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p],
     "fg_mask_confusion": [fg_view, fg_view, C.c_void_p, C.c_void_p],
+    "fg_lpips_stem": [fg_sview, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, fg_view, C.c_int, C.c_void_p],
+    "fg_maxpool3s2": [fg_view, fg_view, C.c_void_p],
+    "fg_lpips_workspace_doubles": [C.c_int, C.c_int, C.c_int],
+    "fg_lpips_layer": [fg_view, fg_view, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "fg_maxpool2": [fg_view, fg_view, C.c_void_p],
     "fg_maxpool2_bwd": [fg_view, fg_view, fg_view, C.c_void_p, C.c_void_p],
     "fg_bce_logits_workspace_doubles": [],
@@ -211,7 +215,8 @@ SIGNATURES = {
 RESTYPES = {"fg_bernoulli_mt_workspace_words": C.c_longlong, "fg_last_error": C.c_char_p, "fg_last_launch": C.c_char_p, "fg_in_workspace_doubles": C.c_longlong, "fg_bn_workspace_doubles": C.c_longlong,
             "fg_ssim_workspace_doubles": C.c_longlong, "fg_sq_err_workspace_doubles": C.c_longlong,
             "fg_channel_sum_workspace_doubles": C.c_longlong, "fg_bce_logits_workspace_doubles": C.c_longlong,
-            "fg_in_partials_workspace_doubles": C.c_longlong, "fg_conv1x1_wgrad_workspace_floats": C.c_longlong}
+            "fg_in_partials_workspace_doubles": C.c_longlong, "fg_conv1x1_wgrad_workspace_floats": C.c_longlong,
+            "fg_lpips_workspace_doubles": C.c_longlong}
 
 _lib = None
 

@@ -8,11 +8,24 @@ averaged over batches), and the segmentation U-Net's flood masks of both images 
 confusion counts; at the end MSE / accuracy / F1 / precision / recall of the flood and no-flood masks
 over every pixel seen (the reference concatenates the flattened masks, which is the same counts).
 
-LPIPS (torchmetrics' LearnedPerceptualImagePatchSimilarity) needs pretrained VGG/AlexNet weights that
-no offline image can supply: it is reported as NaN.  torchmetrics itself is not installed here, so the
-metric formulas follow its published 1.2.0 algorithm and their parity is unpinned (the oracle restates
-the same algorithm: oracle/evaluation.py)."""
+LPIPS (torchmetrics' LearnedPerceptualImagePatchSimilarity with its defaults: net_type="alex",
+reduction="mean", normalize=False, models/model.py:404-406) needs pretrained AlexNet + "lin" weights that
+this repository cannot ship: without them it is reported as NaN.  Given a weights file (lpips_weights=, see
+load_lpips_weights for the accepted layouts) the LPIPS class computes it on the device: the scaling layer,
+AlexNet's stem conv and the pools and the per-tap distance in their own kernels (csrc/lpips.hip), the other
+four convs on the conv engine.  The formula implemented, on the [0, 1] images as they are (no 2x - 1 rescale):
+  1. x' = (x - shift) / scale per RGB channel, shift (-0.030, -0.088, -0.188), scale (0.458, 0.448, 0.450);
+  2. torchvision AlexNet `features` with zero padding applied after the scaling, five taps each after a ReLU:
+     Conv(3,64,11,s4,p2) | MaxPool(3,s2) Conv(64,192,5,p2) | MaxPool(3,s2) Conv(192,384,3,p1) |
+     Conv(384,256,3,p1) | Conv(256,256,3,p1);
+  3. per tap k, n(f) = sqrt(1e-8 + sum_c f_c^2), d_k[i] = mean_{y,x} sum_c w_k[c] (f0_c / n(f0) - f1_c / n(f1))^2;
+  4. LPIPS[i] = sum_k d_k[i]; one call = one batch = the mean over i, then averaged over batches.
+
+torchmetrics itself is not installed here (nor is lpips, nor any pretrained weights), so the metric formulas
+follow its published 1.2.0 algorithm and their parity is unpinned (the oracle restates the same algorithm:
+oracle/evaluation.py; for LPIPS tests/lpips_oracle.py)."""
 import math
+import os
 import time
 
 import numpy as np
@@ -20,6 +33,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import plans as PL
 from .segmentation import SegmentationModel, unit_image
 
 MS_SSIM_BETAS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
@@ -39,8 +53,9 @@ def gaussian11(sigma=1.5, size=11):
 class ImageMetrics:
     """Device PSNR / SSIM / MS-SSIM of [N, C, H, W] images already in [0, 1] (contiguous NCHW)."""
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", lpips=None):
         self.device = torch.device(device)
+        self._lpips = _as_lpips(lpips, device)
         self.g = gaussian11().to(self.device)
         self.betas = torch.tensor(MS_SSIM_BETAS, dtype=torch.float64, device=self.device)
         self.c1, self.c2 = (K1 * DATA_RANGE) ** 2, (K2 * DATA_RANGE) ** 2
@@ -93,6 +108,168 @@ class ImageMetrics:
                                       L.stream_handle()), "msssim_combine")
         return float(out.mean())
 
+    def lpips(self, a, b):
+        """batch-mean LPIPS (needs ImageMetrics(lpips=weights path / dict / LPIPS object))"""
+        if self._lpips is None:
+            raise RuntimeError("ImageMetrics.lpips needs LPIPS weights: construct ImageMetrics(lpips=...)")
+        return self._lpips(a, b)
+
+
+# ------------------------------------------------------------------------------------------ LPIPS
+
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+# AlexNet features: (index in torchvision's Sequential, lpips slice, out, in, kernel, stride, padding)
+ALEX_CONVS = ((0, 1, 64, 3, 11, 4, 2), (3, 2, 192, 64, 5, 1, 2), (6, 3, 384, 192, 3, 1, 1), (8, 4, 256, 384, 3, 1, 1),
+              (10, 5, 256, 256, 3, 1, 1))
+LPIPS_MIN_SIZE = 31          # the second pool needs a 3 x 3 input: 31 -> 7 -> 3 -> 1
+
+
+def lpips_weight_shapes():
+    """{our fixed name: shape} of the dict load_lpips_weights returns: conv{1..5}.weight / .bias (AlexNet
+    features 0, 3, 6, 8, 10) and lin{0..4}.weight (the taps' 1x1 weights, flattened to [C])"""
+    out = {}
+    for i, (_, _, o, c, k, _, _) in enumerate(ALEX_CONVS):
+        out[f"conv{i + 1}.weight"] = (o, c, k, k)
+        out[f"conv{i + 1}.bias"] = (o,)
+        out[f"lin{i}.weight"] = (o,)
+    return out
+
+
+def load_lpips_weights(path_or_dict):
+    """LPIPS (alex) weights as a plain dict of fp32 CPU tensors under the names of lpips_weight_shapes(), from a
+    file (torch.load(..., map_location="cpu", weights_only=True)) or a state dict in one of these layouts:
+      * lpips / torchmetrics: net.slice1.0 / net.slice2.3 / net.slice3.6 / net.slice4.8 / net.slice5.10
+        .{weight,bias}, lin{0..4}.model.1.weight [1, C, 1, 1]; optionally scaling_layer.shift / .scale (must equal
+        the constants to 1e-6) and the lins.{k}.model.1.weight aliases a module's state_dict() repeats (must equal
+        lin{k}); optionally one extra leading "net." on every key (a metric's state_dict());
+      * parts: torchvision AlexNet's features.{0,3,6,8,10}.{weight,bias} merged with the five lin{k}.model.1.weight;
+      * the returned dict itself.
+    Every shape is checked; a missing key, an unexpected key or a wrong shape raises ValueError naming the key."""
+    sd = path_or_dict
+    if isinstance(sd, (str, os.PathLike)):
+        sd = torch.load(sd, map_location="cpu", weights_only=True)
+    if not isinstance(sd, dict) or not sd:
+        raise ValueError(f"LPIPS weights: expected a state dict (got {type(sd).__name__})")
+    sd = dict(sd)
+    shapes = lpips_weight_shapes()
+    # a metric's state_dict(): every key, the lin keys too, carries one more "net."
+    if all(k.startswith("net.") for k in sd) and any(k.startswith(("net.net.", "net.lin", "net.features."))
+                                                     for k in sd):
+        sd = {k[4:]: v for k, v in sd.items()}
+    if any(k.startswith("net.slice") for k in sd):
+        names = {f"net.slice{sl}.{idx}.{p}": f"conv{i + 1}.{p}" for i, (idx, sl, *_) in enumerate(ALEX_CONVS)
+                 for p in ("weight", "bias")}
+    elif any(k.startswith("features.") for k in sd):
+        names = {f"features.{idx}.{p}": f"conv{i + 1}.{p}" for i, (idx, *_) in enumerate(ALEX_CONVS)
+                 for p in ("weight", "bias")}
+    else:
+        names = {k: k for k in shapes if k.startswith("conv")}
+    own = not any(k.startswith(("net.slice", "features.")) for k in sd)
+    for k in range(5):
+        names[f"lin{k}.weight" if own else f"lin{k}.model.1.weight"] = f"lin{k}.weight"
+    out = {}
+    for src, dst in names.items():
+        if src not in sd:
+            raise ValueError(f"LPIPS weights: missing key {src!r}")
+        want = shapes[dst] if (own or not dst.startswith("lin")) else (1, shapes[dst][0], 1, 1)
+        t = sd.pop(src)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+            raise ValueError(f"LPIPS weights: key {src!r} has shape {tuple(getattr(t, 'shape', ()))}, expected {want}")
+        out[dst] = t.detach().to(torch.float32).reshape(shapes[dst]).contiguous().clone()
+    for src, const in (("scaling_layer.shift", LPIPS_SHIFT), ("scaling_layer.scale", LPIPS_SCALE)):
+        if src in sd:
+            t = sd.pop(src)
+            if t.numel() != 3 or float((t.detach().double().flatten() - torch.tensor(const, dtype=torch.float64))
+                                       .abs().max()) > 1e-6:
+                raise ValueError(f"LPIPS weights: key {src!r} differs from the scaling layer's constants {const}")
+    for k in range(5):
+        src = f"lins.{k}.model.1.weight"
+        if src in sd:
+            t = sd.pop(src)
+            if tuple(t.shape) != (1, shapes[f"lin{k}.weight"][0], 1, 1) or not torch.equal(
+                    t.detach().to(torch.float32).flatten(), out[f"lin{k}.weight"]):
+                raise ValueError(f"LPIPS weights: key {src!r} differs from 'lin{k}.model.1.weight'")
+    if sd:
+        raise ValueError(f"LPIPS weights: unexpected key {sorted(sd)[0]!r}")
+    return out
+
+
+class LPIPS:
+    """torchmetrics LearnedPerceptualImagePatchSimilarity() (alex, mean, normalize=False) on the device, formula as
+    in the module docstring (parity unpinned).  weights: a path or a dict (load_lpips_weights).  The conv weights are
+    packed once per object (and per conv math), the activation buffers cached per input shape."""
+
+    def __init__(self, weights, device="cuda"):
+        self.device = torch.device(device)
+        W = {k: v.to(self.device) for k, v in load_lpips_weights(weights).items()}
+        self.stem_w = W["conv1.weight"].permute(1, 2, 3, 0).contiguous()       # [c][r][s][64]
+        self.conv_w = [W[f"conv{i}.weight"] for i in range(2, 6)]
+        self.bias = [W[f"conv{i}.bias"] for i in range(1, 6)]
+        self.lin = [W[f"lin{k}.weight"] for k in range(5)]
+        self._packs, self._bufs = {}, {}
+
+    def _packed(self, i, c_alloc):
+        """(packed weight, weight map) of conv i + 2 in the current conv math"""
+        key = (L.get_conv_math(), i)
+        if key not in self._packs:
+            m = PL.wmap_conv_fwd(self.conv_w[i].shape, c_alloc)
+            self._packs[key] = (ops.pack_weight(self.conv_w[i], m), m)
+        return self._packs[key]
+
+    def _buffers(self, n, h, w):
+        key = (n, h, w)
+        if key not in self._bufs:
+            dev = self.device
+            h0, w0 = PL.out_size(h, 11, 4, 2), PL.out_size(w, 11, 4, 2)
+            h1, w1 = PL.out_size(h0, 3, 2, 0), PL.out_size(w0, 3, 2, 0)
+            h2, w2 = PL.out_size(h1, 3, 2, 0), PL.out_size(w1, 3, 2, 0)
+            # a padded buffer's border is zeroed here once: the kernels write interiors only
+            self._bufs[key] = dict(
+                t0=PL.Buf.empty(n, h0, w0, 64, 0, dev), p1=PL.Buf.zeros(n, h1, w1, 64, 2, dev),
+                t1=PL.Buf.empty(n, h1, w1, 192, 0, dev), p2=PL.Buf.zeros(n, h2, w2, 192, 1, dev),
+                t2=PL.Buf.zeros(n, h2, w2, 384, 1, dev), t3=PL.Buf.zeros(n, h2, w2, 256, 1, dev),
+                t4=PL.Buf.empty(n, h2, w2, 256, 0, dev), out=torch.empty(n // 2, dtype=torch.float64, device=dev))
+        return self._bufs[key]
+
+    def _conv(self, i, X, Y):
+        k, pad = ALEX_CONVS[i + 1][4], ALEX_CONVS[i + 1][6]
+        wp, m = self._packed(i, X.c)
+        ops.conv([PL.conv_problem(X, pad, k, 1, wp, m, Y, bias=self.bias[i + 1], act=L.FG_ACT_RELU)])
+
+    def per_image(self, a, b):
+        """[N] fp64 LPIPS of each image pair of two [N, 3, H, W] images in [0, 1]"""
+        if a.dim() != 4 or a.shape[1] != 3 or a.shape != b.shape:
+            raise ValueError(f"LPIPS takes two [N, 3, H, W] images of equal shape (got {tuple(a.shape)} and "
+                             f"{tuple(b.shape)})")
+        N, _, H, W = a.shape
+        if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
+            raise ValueError(f"LPIPS (alex) needs images of at least {LPIPS_MIN_SIZE}px (got {H}x{W})")
+        B = self._buffers(2 * N, H, W)
+        for img0, x in ((0, a), (N, b)):                       # output and target as one 2N batch
+            ops.lpips_stem(x, self.stem_w, self.bias[0], B["t0"], img0)
+        ops.maxpool3s2(B["t0"], B["p1"])
+        self._conv(0, B["p1"], B["t1"])
+        ops.maxpool3s2(B["t1"], B["p2"])
+        self._conv(1, B["p2"], B["t2"])
+        self._conv(2, B["t2"], B["t3"])
+        self._conv(3, B["t3"], B["t4"])
+        for k in range(5):
+            f0, f1 = ops.half_views(B[f"t{k}"])
+            ops.lpips_layer(f0, f1, B[f"t{k}"].c, self.lin[k], B["out"], accumulate=k > 0)
+        return B["out"].clone()
+
+    def __call__(self, a, b):
+        """the batch mean (reduction="mean"): one torchmetrics update + compute"""
+        return float(self.per_image(a, b).mean())
+
+
+def _as_lpips(lpips_weights, device):
+    """None, an LPIPS object, or weights (path / dict) -> None or an LPIPS object"""
+    if lpips_weights is None or isinstance(lpips_weights, LPIPS):
+        return lpips_weights
+    return LPIPS(lpips_weights, device)
+
 
 class MaskConfusion:
     """tp / fp / tn / fn of the flood masks over every pixel seen, and the torchmetrics binary metrics
@@ -133,10 +310,10 @@ def extract_input_topography(x, topography):
     return x[:, chans]
 
 
-def score_batch(generator, input_stack, ground_truth, seg, im, confs, sync=True):
+def score_batch(generator, input_stack, ground_truth, seg, im, confs, sync=True, *, with_lpips=False):
     """One batch of models/model.py:388-410 (the segmentation U-Net sees the output, then the target, as
     there): returns (PSNR, SSIM, MS-SSIM, inference seconds); the masks go into every MaskConfusion of
-    confs."""
+    confs.  with_lpips=True (im built with lpips=): returns (PSNR, SSIM, MS-SSIM, inference seconds, LPIPS)."""
     start = time.time()
     torch.manual_seed(47)
     with torch.no_grad():
@@ -150,40 +327,47 @@ def score_batch(generator, input_stack, ground_truth, seg, im, confs, sync=True)
     true_logits = seg.logits_from_buf(gt_buf)
     for conf in confs:
         conf.update(pred_logits, true_logits)
-    return im.psnr(go, gt), im.ssim(go, gt), im.ms_ssim(go, gt), t
+    vals = (im.psnr(go, gt), im.ssim(go, gt), im.ms_ssim(go, gt), t)
+    return vals + (im.lpips(go, gt),) if with_lpips else vals
 
 
-def calculate_metrics(generator, loader, seg_model, topography="all", device="cuda"):
+_BATCH_KEYS = ("PSNR", "SSIM", "MS-SSIM", "Inference", "LPIPS")
+
+
+def calculate_metrics(generator, loader, seg_model, topography="all", device="cuda", lpips_weights=None):
     """The device counterpart of Model.calculate_metrics: {metric: value} averaged as the reference
-    does (image metrics over batches, mask metrics over all pixels)."""
-    im, conf = ImageMetrics(device), MaskConfusion(device)
-    per = {k: [] for k in ("PSNR", "SSIM", "MS-SSIM", "Inference")}
+    does (image metrics over batches, mask metrics over all pixels).  lpips_weights (a path, a dict or an
+    LPIPS object): LPIPS is the mean of the per-batch values; None: NaN."""
+    im, conf = ImageMetrics(device, lpips=lpips_weights), MaskConfusion(device)
+    with_lpips = lpips_weights is not None
+    per = {k: [] for k in _BATCH_KEYS}
     for input_stack, ground_truth, _ in loader:
         x = extract_input_topography(input_stack, topography).to(device)
         y = ground_truth.to(device)
-        p, s, m, t = score_batch(generator, x, y, seg_model, im, [conf])
-        for k, v in zip(("PSNR", "SSIM", "MS-SSIM", "Inference"), (p, s, m, t)):
+        for k, v in zip(_BATCH_KEYS, score_batch(generator, x, y, seg_model, im, [conf], with_lpips=with_lpips)):
             per[k].append(v)
-    res = {k: float(np.mean(v)) for k, v in per.items() if k != "Inference"}
-    res["LPIPS"] = float("nan")
+    res = {k: float(np.mean(v)) for k, v in per.items() if k not in ("Inference", "LPIPS")}
+    res["LPIPS"] = float(np.mean(per["LPIPS"])) if with_lpips else float("nan")
     res.update(conf.compute())
     res["Inference"] = float(np.mean(per["Inference"]))
     return {k: res[k] for k in METRIC_NAMES + ["Inference"]}
 
 
-def compare_metrics(generators, loader, seg_model, compare="model", device="cuda"):
+def compare_metrics(generators, loader, seg_model, compare="model", device="cuda", lpips_weights=None):
     """ModelsGroup.compare_metrics (models/group.py:114-221): {generator name: {metric: value}} plus the
     per-disaster metrics {generator name: {disaster: {metric: value}}} -- the mask metrics over that
-    disaster's pixels and the batch means of PSNR / SSIM / MS-SSIM (LPIPS NaN) over its batches, as the
-    reference's grouped table (group.py:211-221).  compare="topography": the
+    disaster's pixels and the batch means of PSNR / SSIM / MS-SSIM / LPIPS (NaN without lpips_weights: a path, a
+    dict or an LPIPS object) over its batches, as the reference's grouped table (group.py:211-221).
+    compare="topography": the
     generators are keyed by topography ("All", "DEM", "Flow accumulation", "Distance to rivers", "Map",
     "None") and see the matching channels of one 9-channel input (models/group.py:83-94)."""
     topo_keys = {"All": "all", "DEM": "dem", "Flow accumulation": "flow", "Distance to rivers": "river", "Map": "map",
                  "None": None}
-    im = ImageMetrics(device)
+    im = ImageMetrics(device, lpips=lpips_weights)
+    with_lpips = lpips_weights is not None
     conf = {g: MaskConfusion(device) for g in generators}
     grouped = {}
-    per = {g: {k: [] for k in ("PSNR", "SSIM", "MS-SSIM", "Inference")} for g in generators}
+    per = {g: {k: [] for k in _BATCH_KEYS} for g in generators}
     disasters = []
     for input_stack, ground_truth, names in loader:
         x = input_stack.to(device)
@@ -195,13 +379,13 @@ def compare_metrics(generators, loader, seg_model, compare="model", device="cuda
             key = (g, disaster)
             if key not in grouped:
                 grouped[key] = MaskConfusion(device)
-            im_vals = score_batch(gen, xi, y, seg_model, im, [conf[g], grouped[key]])
-            for k, v in zip(("PSNR", "SSIM", "MS-SSIM", "Inference"), im_vals):
+            im_vals = score_batch(gen, xi, y, seg_model, im, [conf[g], grouped[key]], with_lpips=with_lpips)
+            for k, v in zip(_BATCH_KEYS, im_vals):
                 per[g][k].append(v)
     out = {}
     for g in generators:
-        res = {k: float(np.mean(v)) for k, v in per[g].items() if k != "Inference"}
-        res["LPIPS"] = float("nan")
+        res = {k: float(np.mean(v)) for k, v in per[g].items() if k not in ("Inference", "LPIPS")}
+        res["LPIPS"] = float(np.mean(per[g]["LPIPS"])) if with_lpips else float("nan")
         res.update(conf[g].compute())
         inf = per[g]["Inference"][5:] if g == next(iter(generators)) else per[g]["Inference"]   # group.py:198-200
         res["Inference"] = float(np.mean(inf)) if inf else float("nan")
@@ -209,8 +393,8 @@ def compare_metrics(generators, loader, seg_model, compare="model", device="cuda
     by_disaster = {}
     for (g, d), c in grouped.items():
         vals = {k: float(np.mean([v for v, dd in zip(per[g][k], disasters) if dd == d]))
-                for k in ("PSNR", "SSIM", "MS-SSIM")}
-        vals["LPIPS"] = float("nan")
+                for k in ("PSNR", "SSIM", "MS-SSIM") + (("LPIPS",) if with_lpips else ())}
+        vals.setdefault("LPIPS", float("nan"))
         vals.update(c.compute())
         by_disaster.setdefault(g, {})[d] = vals
     return out, by_disaster

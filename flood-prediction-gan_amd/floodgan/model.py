@@ -388,10 +388,11 @@ class Model:
             self.scheduler_discriminator.step()
             self.save_results(epoch, losses, t0)
 
-    def calculate_metrics(self, use_test_data=False, seg_model_path=None, seg_model=None):
+    def calculate_metrics(self, use_test_data=False, seg_model_path=None, seg_model=None, lpips_weights=None):
         """models/model.py:363-422 on the device (floodgan.evaluate): the generator (pre_to_post for the
         cycle models) over the validation / test loader, PSNR / SSIM / MS-SSIM of its [0, 1] outputs,
-        the segmentation U-Net's flood masks of output and target and their binary metrics.  Returns
+        the segmentation U-Net's flood masks of output and target and their binary metrics; LPIPS when
+        lpips_weights (a path, a dict or a floodgan.evaluate.LPIPS object) is given, else NaN.  Returns
         the one-row DataFrame the reference prints (and writes it under data_path/metrics/ when set)."""
         import pandas as pd
 
@@ -401,7 +402,7 @@ class Model:
             raise RuntimeError("assign Model.val_loader / Model.test_loader first (floodgan.data.create_flood_dataset)")
         seg = seg_model if seg_model is not None else segmentation_model(seg_model_path, self.device)
         gen = self.pre_to_post_generator if self.model_is_cycle else self.generator
-        res = calculate_metrics(gen, loader, seg, self.topography, self.device)
+        res = calculate_metrics(gen, loader, seg, self.topography, self.device, lpips_weights=lpips_weights)
         # the reference's table (models/model.py:419-422): one row, a "0" index column, written to
         # create_path("metric")
         df = pd.DataFrame([(k, v) for k, v in res.items()]).set_index(0).transpose()

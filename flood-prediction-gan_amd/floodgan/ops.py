@@ -1034,6 +1034,48 @@ def bce_logits(logits, target, gscale, grad, loss_out, correct_out=None):
                                  L.ptr(correct_out), L.ptr(work), L.stream_handle()), "bce_logits")
 
 
+# ------------------------------------------------------------------ LPIPS (evaluate.LPIPS)
+
+def lpips_stem(x, wt, bias, Y, img0=0):
+    """Y[img0 : img0 + N] (64 channels) = relu(AlexNet conv1 of the lpips-scaled [N, 3, H, W] image x in [0, 1]);
+    wt: conv1's weight as [3, 11, 11, 64] (weight.permute(1, 2, 3, 0).contiguous())"""
+    L.require_device(x, "LPIPS image")
+    N, Cc, H, W = x.shape
+    if Cc != 3 or tuple(wt.shape) != (3, 11, 11, 64) or not wt.is_contiguous() or bias.numel() != 64:
+        raise RuntimeError(f"lpips_stem: a 3-channel image and a [3, 11, 11, 64] weight (got {tuple(x.shape)}, "
+                           f"{tuple(wt.shape)})")
+    _wrote(Y)
+    L.check(_lib().fg_lpips_stem(sview(x), N, H, W, L.ptr(wt), L.ptr(bias), view(Y), img0, L.stream_handle()),
+            "lpips_stem")
+
+
+def maxpool3s2(src, dst):
+    """nn.MaxPool2d(3, 2) of src's interior into dst's interior (dst's border is left as it is)"""
+    _wrote(dst)
+    L.check(_lib().fg_maxpool3s2(view(src), view(dst), L.stream_handle()), "maxpool3s2")
+
+
+def half_views(B):
+    """the fg_views of images [0, n / 2) and [n / 2, n) of a Buf (output and target halves of one batch)"""
+    n = B.n // 2
+    assert B.n == 2 * n
+    return (L.fg_view(B.t.data_ptr(), n, B.h, B.w, B.c, B.pad),
+            L.fg_view(B.t.data_ptr() + 4 * n * B.s_img, n, B.h, B.w, B.c, B.pad))
+
+
+def lpips_layer(f0, f1, c, w, out, accumulate=False):
+    """out[i] (+)= one LPIPS tap's distance of image i of f0 vs f1 (Bufs or fg_views of equal geometry); w: the
+    tap's [c] lin weight; out: fp64 [n]"""
+    v0, v1 = (view(f) if isinstance(f, (Buf, Slice)) else f for f in (f0, f1))
+    if out.dtype != torch.float64 or out.numel() != v0.n or not out.is_contiguous() or w.numel() != c:
+        raise RuntimeError(f"lpips_layer: out must be a contiguous fp64 [{v0.n}] tensor and w hold {c} weights")
+    L.require_device(w, "LPIPS lin weight")
+    work = torch.empty(int(_lib().fg_lpips_workspace_doubles(v0.n, v0.h, v0.w)), dtype=torch.float64,
+                       device=out.device)
+    L.check(_lib().fg_lpips_layer(v0, v1, c, L.ptr(w), L.ptr(out), int(accumulate), L.ptr(work), L.stream_handle()),
+            "lpips_layer")
+
+
 # ------------------------------------------------------------------ tail / losses / adam
 
 def tail_fwd(cl, al, x, out, mask):

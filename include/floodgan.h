@@ -620,6 +620,28 @@ int fg_sq_err_sum(const float* a, const float* b, long long total, double* out, 
  * (sigmoid(logit) > 0.5, channel 0 of each view) of pred vs true segmentation logits. */
 int fg_mask_confusion(fg_view pred_logits, fg_view true_logits, unsigned long long* counts, hipStream_t stream);
 
+/* LPIPS, torchmetrics LearnedPerceptualImagePatchSimilarity(net_type="alex", normalize=False) as the reference
+ * calls it (models/model.py:404-406).  Its four 5x5 / 3x3 convs run on fg_conv_fwd; these are the other pieces.
+ * fg_lpips_stem: y(img0 + i, :, :, 0..63) = relu(conv(pad2((x_i - shift) / scale), wt) + bias) for the n images of
+ * the strided [n, 3, h, w] view x in [0, 1]: the lpips scaling layer (shift (-0.030, -0.088, -0.188), scale (0.458,
+ * 0.448, 0.450)), then AlexNet's Conv2d(3, 64, 11, stride 4, padding 2) + ReLU; the zero padding follows the
+ * scaling, so a tap outside the image contributes exactly 0.  wt: the weight transposed to [c][r][s][64]
+ * (weight.permute(1, 2, 3, 0), 16-B aligned); y: 64 channels, y.h = (h + 4 - 11) / 4 + 1 (interior written). */
+int fg_lpips_stem(fg_sview x, int n, int h, int w, const float* wt, const float* bias, fg_view y, int img0,
+                  hipStream_t stream);
+/* nn.MaxPool2d(3, stride 2) (floor, no padding) over src's interior into dst's interior, dst.h = (src.h - 3) / 2
+ * + 1; dst's border (the next conv's zero padding) is not touched.  Maxima are taken with fmaxf: a NaN is not
+ * propagated as torch would (every input here is a ReLU output). */
+int fg_maxpool3s2(fg_view src, fg_view dst, hipStream_t stream);
+/* One LPIPS tap: out[i] (=, or += when accumulate) (1 / (h w)) sum_{y,x} sum_{ch < c} w[ch] (f0_ch / n(f0) -
+ * f1_ch / n(f1))^2 over the interiors of image i of f0 and f1 (equal geometry; the two halves of one 2N batch are
+ * two views of one buffer), n(f) = sqrt(1e-8 + sum_ch f_ch^2); c a multiple of 64 up to 512, w 16-B aligned.
+ * fp32 inside a pixel, fp64 across pixels and blocks in a fixed order (no floating-point atomics: two runs are
+ * bit-identical).  work: fg_lpips_workspace_doubles(n, h, w) doubles. */
+long long fg_lpips_workspace_doubles(int n, int h, int w);
+int fg_lpips_layer(fg_view f0, fg_view f1, int c, const float* w, double* out, int accumulate, double* work,
+                   hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------- */
 /* tile data path                                                    */
 /* ---------------------------------------------------------------------------------------- */
