@@ -88,7 +88,7 @@ class ImageMetrics:
         contrast sensitivity of the first four and the SSIM of the last, F.avg_pool2d(2) in between"""
         N, C, H, W = a.shape
         S = len(MS_SSIM_BETAS)
-        if H < 2 ** S or W < 2 ** S or H // (S - 1) ** 2 <= 10:
+        if H < 2 ** S or W < 2 ** S or H // (S - 1) ** 2 <= 10 or W // (S - 1) ** 2 <= 10:
             raise ValueError(f"MS-SSIM needs images larger than {(S - 1) ** 2 * 10}px (got {H}x{W})")
         cs_all = torch.empty(S - 1, N, dtype=torch.float64, device=self.device)
         lib = L.load()

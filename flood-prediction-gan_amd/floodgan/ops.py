@@ -1124,7 +1124,9 @@ def l1(a, b, gscale, loss_out, g=None, accumulate=False, loss_scale=1.0):
 def adam_step(entries, lr, beta1, beta2, eps, step):
     """entries: list of (param, grad, exp_avg, exp_avg_sq) tensors sharing `step`.  The kernel
     also raises a fresh absmax slot per parameter (the next weight packing's scale source),
-    cached on the parameter with its version counter (see absmax)."""
+    cached on the parameter with its version counter (see absmax).  Empty parameters (a null
+    data_ptr; torch.optim.Adam steps them as a no-op) are skipped."""
+    entries = [e for e in entries if e[0].numel() > 0]
     if not entries:
         return
     arr = (L.fg_adam_tensor * len(entries))()

@@ -12,7 +12,10 @@ __graft_entry__.smoke() and bench.py's cpu_baseline leg may import it).
                   torchmetrics is not installed in this image: these restate its published algorithm
                   (gaussian 11x11 sigma 1.5 window over reflect-padded inputs, cropped back; five MS-SSIM
                   scales with betas (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), normalize="relu") -- PARITY
-                  UNPINNED for the metric formulas.
+                  UNPINNED against torchmetrics itself; the formulas are held to closed forms (constant and
+                  scaled images, the window, the relu clamp: tests/test_oracle_evaluation_cpu.py).  Every
+                  operation runs in `dtype` (float64: the reference value; float32: torchmetrics' own
+                  precision, from which the GPU tests derive their tolerances).
 """
 import torch
 import torch.nn.functional as F
@@ -67,12 +70,13 @@ def _gaussian(size=11, sigma=1.5, dtype=torch.float64):
     return (g / g.sum()).unsqueeze(0)
 
 
-def _ssim_and_cs(a, b, data_range=1.0, k1=0.01, k2=0.03):
-    """per-image (ssim, cs) of torchmetrics 1.2.0 _ssim_update"""
-    a, b = a.clamp(0, 1).double(), b.clamp(0, 1).double()
+def _ssim_maps(a, b, data_range=1.0, k1=0.01, k2=0.03, dtype=torch.float64):
+    """the [N, C, H - 10, W - 10] maps of torchmetrics 1.2.0 _ssim_update over the windows inside the image:
+    (ssim map, contrast-sensitivity map, windowed variance of a), every operation in `dtype`"""
+    a, b = a.clamp(0, 1).to(dtype), b.clamp(0, 1).to(dtype)
     C = a.shape[1]
     c1, c2 = (k1 * data_range) ** 2, (k2 * data_range) ** 2
-    g = _gaussian()
+    g = _gaussian(dtype=dtype)
     kernel = torch.matmul(g.t(), g).expand(C, 1, 11, 11)
     pad = 5
     a, b = F.pad(a, (pad,) * 4, mode="reflect"), F.pad(b, (pad,) * 4, mode="reflect")
@@ -84,23 +88,31 @@ def _ssim_and_cs(a, b, data_range=1.0, k1=0.01, k2=0.03):
     ssim_map = ((2 * mu_ab + c1) * upper) / ((mu_a2 + mu_b2 + c1) * lower)
     cs_map = upper / lower
     crop = (Ellipsis, slice(pad, -pad), slice(pad, -pad))
+    return ssim_map[crop], cs_map[crop], (e_aa - mu_a2)[crop]
+
+
+def _ssim_and_cs(a, b, data_range=1.0, k1=0.01, k2=0.03, dtype=torch.float64):
+    """per-image (ssim, cs) of torchmetrics 1.2.0 _ssim_update, every operation in `dtype` (float64: the
+    reference value; float32: what torchmetrics itself computes, the measure of the formula's fp32 spread)"""
+    ssim_map, cs_map, _ = _ssim_maps(a, b, data_range, k1, k2, dtype)
     n = ssim_map.shape[0]
-    return ssim_map[crop].reshape(n, -1).mean(-1), cs_map[crop].reshape(n, -1).mean(-1)
+    return ssim_map.reshape(n, -1).mean(-1), cs_map.reshape(n, -1).mean(-1)
 
 
-def ssim(a, b):
-    return float(_ssim_and_cs(a, b)[0].mean())
+def ssim(a, b, dtype=torch.float64):
+    return float(_ssim_and_cs(a, b, dtype=dtype)[0].mean())
 
 
-def ms_ssim(a, b):
+def ms_ssim(a, b, dtype=torch.float64):
+    a, b = a.to(dtype), b.to(dtype)             # the pooling between the scales runs in `dtype` too
     cs_list = []
     for _ in range(len(BETAS)):
-        sim, cs = _ssim_and_cs(a, b)
+        sim, cs = _ssim_and_cs(a, b, dtype=dtype)
         cs_list.append(torch.relu(cs))
         a, b = F.avg_pool2d(a, 2), F.avg_pool2d(b, 2)
     cs_list[-1] = torch.relu(sim)
     stack = torch.stack(cs_list)
-    betas = torch.tensor(BETAS, dtype=torch.float64).view(-1, 1)
+    betas = torch.tensor(BETAS, dtype=dtype).view(-1, 1)
     return float(torch.prod(stack ** betas, 0).mean())
 
 

@@ -107,3 +107,89 @@ def test_evaluate_host_helpers():
     assert extract_input_topography(x[:, :4], "dem").shape[1] == 4
     with pytest.raises(ValueError):
         extract_input_topography(x[:, :5], "map")
+
+
+# ------------------------------------------------------------------ the metric formulas, pinned by closed forms
+#
+# torchmetrics is absent, so the restatements are held to what the published SSIM definition gives in closed
+# form: with a normalised window, constant images have zero windowed (co)variance, and b = s * a has
+# sigma_b^2 = s^2 sigma_a^2, sigma_ab = s sigma_a^2.
+
+C1, C2 = 0.01 ** 2, 0.03 ** 2
+
+
+def test_gaussian_window_closed_form():
+    g = OE._gaussian().flatten()
+    assert g.dtype == torch.float64 and g.numel() == 11
+    assert torch.equal(g, g.flip(0))
+    assert float(g.sum()) == pytest.approx(1.0, abs=1e-15)
+    for i in range(10):
+        k = i - 5                                    # tap offsets -5 .. 5: g(k + 1) / g(k)
+        assert float(g[i + 1] / g[i]) == pytest.approx(np.exp(-(2 * k + 1) / (2 * 1.5 ** 2)), rel=1e-12)
+    g32 = OE._gaussian(dtype=torch.float32)
+    assert g32.dtype == torch.float32 and torch.allclose(g32.double().flatten(), g, atol=1e-7)
+
+
+@pytest.mark.parametrize("alpha,beta", [(0.3, 0.3), (0.2, 0.9), (0.0, 1.0), (0.5, 0.0)])
+def test_ssim_constant_images_closed_form(alpha, beta):
+    a = torch.full((2, 3, 17, 23), alpha, dtype=torch.float64)
+    b = torch.full((2, 3, 17, 23), beta, dtype=torch.float64)
+    s, cs = OE._ssim_and_cs(a, b)
+    want = (2 * alpha * beta + C1) / (alpha ** 2 + beta ** 2 + C1)
+    assert s.shape == (2,) and float((s - want).abs().max()) < 1e-9
+    assert float((cs - 1.0).abs().max()) < 1e-9
+    assert OE.ssim(a, b) == pytest.approx(want, abs=1e-9)
+
+
+@pytest.mark.parametrize("s", [0.25, 0.6, 1.0])
+def test_cs_map_of_scaled_image_closed_form(s):
+    g = torch.Generator().manual_seed(11)
+    a = torch.rand((2, 3, 19, 29), generator=g, dtype=torch.float64)
+    ssim_map, cs_map, var_a = OE._ssim_maps(a, s * a)
+    assert cs_map.shape == (2, 3, 9, 19) and var_a.shape == cs_map.shape
+    assert float(var_a.min()) > 1e-2                 # noise: the variance term dominates c2
+    want = (2 * s * var_a + C2) / ((1 + s * s) * var_a + C2)
+    assert float((cs_map - want).abs().max()) < 1e-9
+    # the windowed variance itself, against a direct evaluation of one window
+    w = OE._gaussian().flatten()
+    w2 = torch.outer(w, w)
+    patch = a[1, 2, 3:14, 7:18]
+    mu = float((w2 * patch).sum())
+    assert float(var_a[1, 2, 3, 7]) == pytest.approx(float((w2 * patch * patch).sum()) - mu * mu, abs=1e-12)
+    # per image: the mean of the maps over channels and windows
+    sim, cs = OE._ssim_and_cs(a, s * a)
+    assert float((cs - cs_map.reshape(2, -1).mean(-1)).abs().max()) < 1e-15
+    assert float((sim - ssim_map.reshape(2, -1).mean(-1)).abs().max()) < 1e-15
+
+
+def test_ms_ssim_relu_clamp_and_dtype():
+    g = torch.Generator().manual_seed(13)
+    a = torch.rand((2, 3, 177, 203), generator=g, dtype=torch.float64)
+    _, cs = OE._ssim_and_cs(a, 1 - a)
+    assert float(cs.max()) < -0.9                    # anti-correlated: cs = (c2 - 2 var) / (c2 + 2 var)
+    assert OE.ms_ssim(a, 1 - a) == 0.0
+    b = (1 - a).clone()
+    b[1] = a[1]
+    assert OE.ms_ssim(a, b) == pytest.approx(0.5, abs=1e-12)
+    # fp32 inputs are pooled in float64 too: the value is that of the same numbers passed as doubles
+    a32 = a.float()
+    b32 = (a32 + 0.15 * torch.randn(a32.shape, generator=g)).clamp(0, 1)
+    assert OE.ms_ssim(a32, b32) == OE.ms_ssim(a32.double(), b32.double())
+    assert OE.ssim(a32, b32) == OE.ssim(a32.double(), b32.double())
+    # dtype=float32 runs the whole formula in fp32: close to, but not the same as, the float64 value
+    lo = OE.ms_ssim(a32, b32, dtype=torch.float32)
+    assert lo != OE.ms_ssim(a32, b32) and abs(lo - OE.ms_ssim(a32, b32)) < 1e-5
+
+
+def test_host_side_argument_rules():
+    """checks the device path makes before any launch: MS-SSIM's size rule on both sides (torchmetrics:
+    side // 16 > 10), and an Adam group of empty parameters being a no-op"""
+    from floodgan import ops
+    from floodgan.evaluate import ImageMetrics
+    im = ImageMetrics("cpu")
+    for h, w in ((191, 161), (161, 191), (160, 160), (31, 400), (400, 31)):
+        x = torch.zeros(1, 3, h, w)
+        with pytest.raises(ValueError):
+            im.ms_ssim(x, x)
+    e = torch.empty(0)
+    assert ops.adam_step([(e, e, e, e)], 2e-4, 0.5, 0.999, 1e-8, 1) is None
