@@ -32,6 +32,7 @@ __device__ __forceinline__ void absmax_flush(unsigned m, unsigned* out) {
         for (int i = 1; i < NT / 64; ++i) r = max(r, red[i]);
         atomicMax(out + (blockIdx.x & (FG_AMAX_SHARDS - 1)), r);
     }
+    __syncthreads();    // red[] is free again: bn_apply_kernel flushes two slots in a row
 }
 __device__ __forceinline__ unsigned absbits4(const f32x4& v) {
     return max(max(__float_as_uint(v[0]) & 0x7fffffffu, __float_as_uint(v[1]) & 0x7fffffffu),
