@@ -56,6 +56,10 @@ __device__ __forceinline__ size_t vidx(const fg_view& v, int n, int y, int x) {
     return ((size_t)(n * hp + y + v.pad) * wp + (x + v.pad)) * (size_t)v.c_alloc;
 }
 
+// The flood decision of a segmentation logit, sigmoid(logit) > 0.5 in fp32 (models/segmentation_model.py:244-246):
+// one function for the confusion counts (metrics.hip) and the rendered masks (render.hip).
+__device__ __forceinline__ bool flood(float logit) { return 1.f / (1.f + expf(-logit)) > 0.5f; }
+
 inline size_t view_elems(const fg_view& v) {
     return (size_t)v.n * (v.h + 2 * v.pad) * (v.w + 2 * v.pad) * v.c_alloc;
 }

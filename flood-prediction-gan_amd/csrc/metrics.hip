@@ -166,8 +166,6 @@ __global__ void sum_partials_kernel(const double* __restrict__ part, int nparts,
     }
 }
 
-__device__ __forceinline__ bool flood(float logit) { return 1.f / (1.f + expf(-logit)) > 0.5f; }
-
 // counts[0..3] += tp, fp, tn, fn of pred vs true masks (channel 0 of each view)
 __global__ void mask_confusion_kernel(fg_view pred, fg_view truth, unsigned long long* counts) {
     const long long total = (long long)pred.n * pred.h * pred.w;
@@ -178,8 +176,8 @@ __global__ void mask_confusion_kernel(fg_view pred, fg_view truth, unsigned long
         const long long r = i / pred.w;
         const int y = (int)(r % pred.h);
         const int ni = (int)(r / pred.h);
-        const bool p = flood(pred.ptr[fg::vidx(pred, ni, y, x)]);
-        const bool t = flood(truth.ptr[fg::vidx(truth, ni, y, x)]);
+        const bool p = fg::flood(pred.ptr[fg::vidx(pred, ni, y, x)]);
+        const bool t = fg::flood(truth.ptr[fg::vidx(truth, ni, y, x)]);
         c[p ? (t ? 0 : 1) : (t ? 3 : 2)] += 1;
     }
     __shared__ unsigned red[4][NT / 64];

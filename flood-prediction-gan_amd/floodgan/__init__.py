@@ -6,7 +6,8 @@ the Model/train_paired API mirror the reference, the arithmetic runs in hand-wri
 kernels (libfloodgan.so, C-ABI in include/floodgan.h).  Around it: the cycle models
 (train_cycle), the tile data path (floodgan.data), Pix2Pix (U-Net-256 + BatchNorm PatchGAN) and the
 evaluation path (segmentation U-Net, device metrics: floodgan.evaluate); torch.library operators in
-floodgan.custom_ops.
+floodgan.custom_ops; pictures of predictions, attention and flood masks as PNG files
+(floodgan.render, floodgan.png: converted and composed on the device, encoded on the host).
 """
 from ._lib import load as load_library  # noqa: F401
 from .model_architectures import (AttentionGANBlock, AttentionGANDiscriminator,  # noqa: F401
@@ -14,10 +15,13 @@ from .model_architectures import (AttentionGANBlock, AttentionGANDiscriminator, 
                                   PairedAttentionBlock, PairedAttentionDiscriminator, PairedAttentionGenerator,
                                   Pix2PixBlock, Pix2PixDiscriminator, Pix2PixGenerator)
 from .segmentation import UNet  # noqa: F401
-from .evaluate import LPIPS, load_lpips_weights  # noqa: F401
+from .evaluate import LPIPS, compare_output_images, load_lpips_weights  # noqa: F401
+from .png import read_png, write_png  # noqa: F401
+from .render import Canvas, colormap_lut, save_image, save_sheet, sheet_layout  # noqa: F401
 
 __all__ = ["PairedAttentionGenerator", "PairedAttentionBlock", "PairedAttentionDiscriminator",
            "AttentionGANGenerator", "AttentionGANBlock", "AttentionGANDiscriminator",
            "CycleGANGenerator", "CycleGANBlock", "CycleGANDiscriminator",
            "Pix2PixGenerator", "Pix2PixBlock", "Pix2PixDiscriminator", "UNet", "load_library", "LPIPS",
-           "load_lpips_weights"]
+           "load_lpips_weights", "Canvas", "colormap_lut", "save_image", "save_sheet", "sheet_layout", "write_png",
+           "read_png", "compare_output_images"]

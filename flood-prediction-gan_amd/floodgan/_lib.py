@@ -76,6 +76,13 @@ class fg_adam_tensor(C.Structure):
 
 FG_TILE_MAX_CH = 16
 
+FG_RENDER_SIGNED, FG_RENDER_UNIT = 0, 1
+FG_SCALAR_UNIT, FG_SCALAR_THRESHOLD, FG_SCALAR_LOGIT = 0, 1, 2
+
+
+class fg_canvas(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("row_bytes", C.c_longlong)]
+
 # fg_set_f3_order's default (csrc/conv_f3.hip g_f3_alt): tests restore it after sweeping the bits
 F3_ORDER_DEFAULT = 31
 
@@ -208,6 +215,10 @@ SIGNATURES = {
     "fg_maxpool2_bwd": [fg_view, fg_view, fg_view, C.c_void_p, C.c_void_p],
     "fg_bce_logits_workspace_doubles": [],
     "fg_bce_logits": [fg_view, C.c_void_p, C.c_float, fg_view, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fg_render_rgb": [fg_sview, C.c_int, C.c_int, C.c_int, C.c_int, fg_canvas, C.c_int, C.c_int, C.c_int, C.c_int,
+                      C.c_void_p],
+    "fg_render_scalar": [fg_sview, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, fg_canvas, C.c_int, C.c_int,
+                         C.c_int, C.c_int, C.c_void_p],
     "fg_tiff_probe": [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "fg_tiff_read": [C.c_char_p, C.c_void_p, C.c_longlong],
     "fg_tile_transform": [C.POINTER(fg_tile_batch), C.c_void_p],

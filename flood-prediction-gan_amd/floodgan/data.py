@@ -300,6 +300,35 @@ def transform_batch(raw, flips, crops, chan, resize, crop, out, tmp=None):
     return out, (meta, tmp)          # keep-alive of the per-call device buffers until the stream passes
 
 
+def load_image_pair(image_name, data_path, dataset_dem, topography, resize, crop, crop_index=0,
+                    csv_path="metadata/dataset_split.csv", device="cuda"):
+    """One named tile pair as the model sees it (models/model.py:482-495, models/group.py:242-255): the input stack
+    {data_path}/dataset_input/{image_name}_{dem}.tif, its DEM string looked up in the split table's {dataset_dem}_DEM
+    column, and the ground truth {data_path}/dataset_output/{image_name}.tif, decoded by read_tile and put through
+    the loader's device transform (no flip; utils.apply_transformations).  Returns (input [1, C, h, w], target
+    [1, 3, h, w], name) on the device, channels-last; with a crop the name gets _{crop_index}."""
+    import pandas as pd
+    split = pd.read_csv(csv_path)
+    rows = split[split["image"] == image_name]
+    if len(rows) == 0:
+        raise ValueError(f"image {image_name!r} is not in {csv_path}")
+    dem_string = rows[f"{dataset_dem}_DEM"].head(1).item()
+    x = read_tile(f"{data_path}/dataset_input/{image_name}_{dem_string}.tif")
+    y = read_tile(f"{data_path}/dataset_output/{image_name}.tif")
+    if x.shape[:2] != y.shape[:2]:
+        raise RuntimeError(f"input {x.shape[:2]} and target {y.shape[:2]} tiles of {image_name!r} differ in size")
+    chan = TOPOGRAPHY_SOURCE_CHANNELS[topography]
+    rh, rw = resized_size(x.shape[0], x.shape[1], resize)
+    _, _, oh, ow = crop_window(rh, rw, crop, 0)
+    dev = torch.device(device)
+    xo = torch.empty((1, len(chan), oh, ow), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    yo = torch.empty((1, 3, oh, ow), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    crops = [crop_index] if crop else None
+    transform_batch(torch.from_numpy(x)[None].to(dev), None, crops, chan, resize, crop, xo)
+    transform_batch(torch.from_numpy(y)[None].to(dev), None, crops, [0, 1, 2], resize, crop, yo)
+    return xo, yo, f"{image_name}_{crop_index}" if crop else image_name
+
+
 # ------------------------------------------------------------------------------------------ dataset
 
 class FloodDataset:

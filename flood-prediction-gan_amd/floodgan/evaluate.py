@@ -361,8 +361,7 @@ def compare_metrics(generators, loader, seg_model, compare="model", device="cuda
     compare="topography": the
     generators are keyed by topography ("All", "DEM", "Flow accumulation", "Distance to rivers", "Map",
     "None") and see the matching channels of one 9-channel input (models/group.py:83-94)."""
-    topo_keys = {"All": "all", "DEM": "dem", "Flow accumulation": "flow", "Distance to rivers": "river", "Map": "map",
-                 "None": None}
+    topo_keys = _TOPOGRAPHY_KEYS
     im = ImageMetrics(device, lpips=lpips_weights)
     with_lpips = lpips_weights is not None
     conf = {g: MaskConfusion(device) for g in generators}
@@ -398,6 +397,41 @@ def compare_metrics(generators, loader, seg_model, compare="model", device="cuda
         vals.update(c.compute())
         by_disaster.setdefault(g, {})[d] = vals
     return out, by_disaster
+
+
+_TOPOGRAPHY_KEYS = {"All": "all", "DEM": "dem", "Flow accumulation": "flow", "Distance to rivers": "river", "Map": "map",
+                    "None": None}
+
+
+def compare_output_images(generators, image_names, *, compare="model", data_path, dataset_dem="best", topography="all",
+                          resize=256, crop=None, crop_index=0, csv_path="metadata/dataset_split.csv", out_path,
+                          device="cuda"):
+    """ModelsGroup.compare_output_images (models/group.py:223-280): one sheet (floodgan.render.save_sheet) with a
+    row per image name -- a trailing _k is its crop index, else crop_index -- and the columns input | ground truth |
+    one per generator of `generators` ({name: module}), each called under torch.manual_seed(47).
+    compare="topography": the tiles are loaded with all nine channels and every generator, keyed by topography as in
+    compare_metrics, sees its channels (extract_input_topography).  Written to out_path (the reference's
+    create_path("image", info=...)); returns the sheet's panels dict."""
+    from .data import load_image_pair
+    from .render import save_sheet
+    xs, ys, names = [], [], []
+    outs = {g: [] for g in generators}
+    for image_name in image_names:
+        final_crop_index = crop_index
+        if len(image_name) >= 2 and image_name[-2] == "_":                      # models/group.py:237-241
+            final_crop_index, image_name = int(image_name[-1]), image_name[:-2]
+        x, y, name = load_image_pair(image_name, data_path, dataset_dem, "all" if compare == "topography" else
+                                     topography, resize, crop, final_crop_index, csv_path=csv_path, device=device)
+        for g, gen in generators.items():
+            xi = extract_input_topography(x, _TOPOGRAPHY_KEYS[g]) if compare == "topography" else x
+            torch.manual_seed(47)
+            with torch.no_grad():
+                outs[g].append(gen(xi.detach().clone()))
+        xs.append(x)
+        ys.append(y)
+        names.append(name)
+    cols = [("Input", "rgb", xs), ("Ground truth", "rgb", ys)] + [(str(g), "rgb", outs[g]) for g in generators]
+    return save_sheet(out_path, cols, names)
 
 
 def segmentation_model(seg_model_path=None, device="cuda"):

@@ -281,6 +281,7 @@ class Model:
                 dataset_subset, dataset_dem, data_path, self.topography, resize=resize, crop=crop,
                 batch_size=batch_size, num_workers=num_workers, csv_path=csv_path, device=device, rank=rank, world=ws)
         self.train_loader, self.val_loader, self.test_loader = train_loader, val_loader, test_loader
+        self.csv_path = csv_path
         self._step = None
 
     def _cycle_nets(self):
@@ -437,7 +438,9 @@ class Model:
         return path.replace("__", "_")
 
     def save_results(self, epoch, losses, epoch_start_time):
-        """models/model.py:322-358 (loss bookkeeping + checkpoint; plots are out of scope)."""
+        """models/model.py:322-361: loss bookkeeping, checkpoint and, every save_images_interval epochs, the sample
+        image sheets (plot_sample_images).  The loss-curve figure (plot_losses) is a matplotlib line chart and is
+        not drawn here."""
         self.current_epoch = epoch
         for key in self.all_losses.keys():
             self.all_losses[key].append(float(np.mean(losses[key[4:]])))
@@ -449,6 +452,115 @@ class Model:
             if self.verbose:
                 print(f"Saving {self.prettify_model_name()} model to {path}")
             torch.save(self.checkpoint(epoch), path)
+        if self.save_images_interval != 0 and epoch % self.save_images_interval == 0:      # models/model.py:360-361
+            self.plot_sample_images(num_images=5, use_test_data=False)
+
+    # ---- pictures (models/model.py:475-596) on floodgan.render: converted and composed on the device
+
+    def plot_image(self, image_name, plot_single_image, plot_image_set, crop_index=0):
+        """models/model.py:475-540: the tile pair `image_name` through the generator (pre_to_post for the cycle
+        models) under torch.manual_seed(47).  plot_single_image: "input", "ground truth", "output" or "attention
+        mask" written with the reference's file names and plt.imsave's bytes; plot_image_set: one sheet input |
+        output | [attention mask] | ground truth (floodgan.render.save_sheet: panels at native resolution, no
+        titles) at create_path("image", info=name).  Returns {"input" | ... | "set": path} of the files written."""
+        import os
+
+        from .data import load_image_pair
+        from .render import save_image, save_sheet
+        x, y, name = load_image_pair(image_name, self.data_path, self.dataset_dem, self.topography, self.resize,
+                                     self.crop, crop_index, csv_path=self.csv_path, device=self.device)
+        generator = self.pre_to_post_generator if self.model_is_cycle else self.generator
+        torch.manual_seed(47)
+        with torch.no_grad():
+            out = generator(x)
+        os.makedirs(f"{self.data_path}/images", exist_ok=True)
+        written = {}
+        if plot_single_image:
+            if plot_single_image == "input":
+                written["input"] = save_image(f"{self.data_path}/images/{name}_input.png", x, "rgb")
+            elif plot_single_image == "ground truth":
+                written["ground truth"] = save_image(f"{self.data_path}/images/{name}_groundTruth.png", y, "rgb")
+            elif plot_single_image == "output":
+                written["output"] = save_image(self.create_path("image", info=name), out, "rgb")
+            elif plot_single_image == "attention mask" and self.model_is_attention:
+                written["attention mask"] = save_image(self.create_path("image", info=f"{name}_attentionMask"),
+                                                       generator.last_attention_mask, "attention")
+            else:
+                raise NotImplementedError("Type of image must be one of 'input', 'ground truth', 'output', or "
+                                          "'attention mask'")
+            if self.verbose:
+                print(f"Saving {plot_single_image} of image '{name}' to {written[plot_single_image]}")
+        if plot_image_set:
+            path = self.create_path("image", info=name)
+            self.last_panels = save_sheet(path, self._sheet_columns([x], [out], [generator.last_attention_mask]
+                                                                    if self.model_is_attention else None, [y]), [name])
+            written["set"] = path
+            if self.verbose:
+                print(f"Saving {name} image set to {path}")
+        return written
+
+    def _sheet_columns(self, inputs, outputs, masks, targets):
+        cols = [("Input", "rgb", inputs), ("Generator Output", "rgb", outputs)]
+        if masks is not None:
+            # the fixed 0..1 range of plot_image; the reference's plot_sample_images lets matplotlib autoscale
+            cols.append(("Attention Mask", "attention", masks))
+        return cols + [("Ground Truth Output", "rgb", targets)]
+
+    def plot_sample_images(self, num_images, use_test_data):
+        """models/model.py:542-596: one sheet per generator and split (training, validation[, test]) of the first
+        num_images loader items (batch element 0 of each batch): input | output | [attention mask] | ground truth,
+        with the reference's seeding (torch.manual_seed(self.seed) before each loader pass, torch.manual_seed(47)
+        before each generator call), its input / output swap for the post-to-pre generator and its file names.  The
+        generators run under torch.no_grad() in the mode they are in.  Returns the paths written."""
+        import os
+
+        from .render import save_sheet
+        if self.model_is_cycle:
+            generators = [("pre-to-post", self.pre_to_post_generator), ("post-to-pre", self.post_to_pre_generator)]
+        else:
+            generators = [("pre-to-post", self.generator)]
+        splits, loaders = ["training", "validation"], [self.train_loader, self.val_loader]
+        if use_test_data:
+            splits, loaders = splits + ["test"], loaders + [self.test_loader]
+        os.makedirs(f"{self.data_path}/images", exist_ok=True)
+        paths = []
+        for label, generator in generators:
+            for split, loader in zip(splits, loaders):
+                if loader is None:
+                    raise RuntimeError(f"plot_sample_images: no {split} loader")
+                xs, outs, masks, ys, names = [], [], [], [], []
+                torch.manual_seed(self.seed)
+                for i, (input_stack, output_image, image_name) in enumerate(loader):
+                    input_stack = input_stack.to(self.device)
+                    output_image = output_image.to(self.device)
+                    if label == "post-to-pre":                                    # models/model.py:566-574
+                        store_output = output_image
+                        if self.topography:
+                            output_image = input_stack[:, :3]
+                            input_stack = torch.cat((store_output, input_stack[:, 3:]), dim=1)
+                        else:
+                            output_image, input_stack = input_stack, store_output
+                    torch.manual_seed(47)
+                    with torch.no_grad():
+                        out = generator(input_stack)
+                    xs.append(input_stack[:1])
+                    outs.append(out[:1])
+                    ys.append(output_image[:1])
+                    if self.model_is_attention:
+                        masks.append(generator.last_attention_mask[:1])
+                    names.append(image_name[0])
+                    if i >= num_images - 1:
+                        break
+                if not names:
+                    raise RuntimeError(f"plot_sample_images: the {split} loader is empty")
+                info = f"{split}{'_' + label if len(generators) > 1 else ''}"
+                path = self.create_path("image", info=info)
+                self.last_panels = save_sheet(path, self._sheet_columns(xs, outs, masks if self.model_is_attention
+                                                                        else None, ys), names)
+                if self.verbose:
+                    print(f"Saving {split} {label + ' ' if len(generators) > 1 else ''}sample images to {path}")
+                paths.append(path)
+        return paths
 
     def checkpoint(self, epoch):
         if self.model_is_cycle:                                   # models/model.py:335-355 (cycle keys)

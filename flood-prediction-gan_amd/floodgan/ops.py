@@ -1146,3 +1146,55 @@ def adam_step(entries, lr, beta1, beta2, eps, step):
         p._fg_amax, p._fg_amax_ver = slot, p._version
     if slots and slots[0] is not None and PACK_CACHE:
         _repack([e[0] for e in entries])
+
+
+# ------------------------------------------------------------------------------------------ pictures (render.hip)
+
+RENDER_SCALAR_KINDS = {"unit": L.FG_SCALAR_UNIT, "threshold": L.FG_SCALAR_THRESHOLD, "logit": L.FG_SCALAR_LOGIT}
+
+
+def canvas_struct(t):
+    """fg_canvas of a uint8 [H, W, 4] device tensor whose pixels are contiguous (rows may have a pitch)"""
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 4 and t.stride(2) == 1
+            and t.stride(1) == 4):
+        raise RuntimeError("floodgan: a canvas is a uint8 [H, W, 4] tensor on a HIP device with contiguous pixels")
+    return L.fg_canvas(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0))
+
+
+def _render_source(t, what):
+    if isinstance(t, Buf):
+        t = t.interior().permute(0, 3, 1, 2)
+    L.require_device(t, what)
+    return t
+
+
+def render_rgb(t, canvas, row=0, col=0, unit=False, step_rows=0, step_cols=0):
+    """fg_render_rgb: channels 0..2 of t ([N, >= 3, H, W] or [>= 3, H, W], any strides, or an NHWC Buf) into the
+    uint8 [H, W, 4] device tensor `canvas`, image i at (row + i step_rows, col + i step_cols)."""
+    t = _render_source(t, "image")
+    if t.dim() == 3:
+        t = t[None]
+    if t.dim() != 4 or t.shape[1] < 3:
+        raise RuntimeError(f"floodgan render_rgb: need [N, >= 3, H, W] (got {tuple(t.shape)})")
+    n, _, h, w = t.shape
+    L.check(L.load().fg_render_rgb(sview(t), n, h, w, L.FG_RENDER_UNIT if unit else L.FG_RENDER_SIGNED,
+                                   canvas_struct(canvas), row, col, step_rows, step_cols, L.stream_handle()),
+            "render_rgb")
+
+
+def render_scalar(t, lut, canvas, row=0, col=0, kind="unit", step_rows=0, step_cols=0):
+    """fg_render_scalar: t ([H, W], [N, H, W], channel 0 of [N, C, H, W], or of an NHWC Buf) through the colormap
+    table lut (uint8 [256, 4] on the device); kind "unit" (the colormap over 0..1), "threshold" (t > 0.5) or "logit"
+    (sigmoid(t) > 0.5, the decision of fg_mask_confusion)."""
+    t = _render_source(t, "image")
+    if t.dim() == 2:
+        t = t[None, None]
+    elif t.dim() == 3:
+        t = t[:, None]
+    if t.dim() != 4:
+        raise RuntimeError(f"floodgan render_scalar: need [H, W], [N, H, W] or [N, C, H, W] (got {tuple(t.shape)})")
+    n, _, h, w = t.shape
+    if not (lut.is_cuda and lut.dtype == torch.uint8 and tuple(lut.shape) == (256, 4) and lut.is_contiguous()):
+        raise RuntimeError("floodgan render_scalar: the colour table is a contiguous uint8 [256, 4] device tensor")
+    L.check(L.load().fg_render_scalar(sview(t), n, h, w, RENDER_SCALAR_KINDS[kind], L.ptr(lut), canvas_struct(canvas),
+                                      row, col, step_rows, step_cols, L.stream_handle()), "render_scalar")

@@ -473,18 +473,24 @@ class SegmentationModel:
     LambdaLR of lambda_rule, starting_epoch resumed from the checkpoint; train_model() runs the fused SegStep.
     The loaders come from floodgan.data.create_masks_dataset when data_path is given, or are assigned
     (train_loader / val_loader / test_loader: iterables of (image, mask, names)).  Every keyword of the reference's
-    constructor is accepted (segment.py passes them all); the plots are out of scope: save_images_interval != 0 and
-    plot_mask_image raise."""
+    constructor is accepted (segment.py passes them all).  Pictures go through floodgan.render: save_images_interval
+    writes the sample sheet (plot_sample_images(num_images=10)) every that many epochs, plot_mask_image(path) the
+    predicted mask of one image; the constructor's plot_mask_image= is kept in mask_image_path for the caller
+    (segment.py calls the method itself); both need a data_path to write under and raise without one.  The
+    loss-curve figure (plot_loss) is a matplotlib line chart and is not drawn here."""
 
     def __init__(self, data_path=None, pretrained_model_path=None, train=False, device="cuda", seed=47,
                  dataset_subset="usa", num_epochs=100, train_on_all=False, save_model_interval=0, verbose=True,
                  save_images_interval=0, plot_mask_image=None, use_test_data=False,
                  csv_path="metadata/masks_metadata.csv"):
-        if save_images_interval != 0 or plot_mask_image:
-            raise NotImplementedError("floodgan: the segmentation model's plots (save_images_interval != 0: "
-                                      "plot_sample_images / plot_loss; plot_mask_image) are out of scope; pass "
-                                      "save_images_interval=0 and plot_mask_image=None")
-        self.save_images_interval, self.use_test_data = 0, use_test_data
+        if (save_images_interval != 0 or plot_mask_image) and data_path is None:
+            # the pictures are written under {data_path}/images (models/segmentation_model.py:102, :205)
+            raise NotImplementedError("floodgan: the segmentation model's pictures (save_images_interval != 0: "
+                                      "plot_sample_images; plot_mask_image) are written under data_path; without "
+                                      "one they are out of scope: pass data_path, or save_images_interval=0 and "
+                                      "plot_mask_image=None")
+        self.save_images_interval, self.use_test_data = save_images_interval, use_test_data
+        self.mask_image_path = plot_mask_image
         self.data_path, self.pretrained_model_path, self.seed = data_path, pretrained_model_path, seed
         self.dataset_subset, self.train_on_all, self.train = dataset_subset, train_on_all, train
         self.save_model_interval, self.verbose, self.csv_path = save_model_interval, verbose, csv_path
@@ -560,7 +566,8 @@ class SegmentationModel:
                 "all_losses": self.all_losses, "all_accuracies": self.all_accuracies}
 
     def save_results(self, epoch, losses, accuracies, epoch_start_time):
-        """models/segmentation_model.py:107-134 (per-epoch means + checkpoint; plots are out of scope)"""
+        """models/segmentation_model.py:107-134: per-epoch means, checkpoint and, every save_images_interval epochs,
+        the sample sheet (plot_sample_images(num_images=10)); the loss-curve figure (plot_loss) is not drawn"""
         import os
         self.current_epoch = epoch
         self.all_losses.append(float(np.mean(losses)))
@@ -568,14 +575,16 @@ class SegmentationModel:
         if self.verbose:
             print(f"Epoch {epoch} ({time.time() - epoch_start_time:.2f} seconds) | Loss = {self.all_losses[-1]:.2f} | "
                   f"Accuracy = {self.all_accuracies[-1]:.2f}")
+        path = None
         if self.save_model_interval != 0 and epoch % self.save_model_interval == 0:
             path = self.create_path("model")
             if self.verbose:
                 print(f"Saving flood segmentation model to {path}")
             os.makedirs(os.path.dirname(path), exist_ok=True)
             torch.save(self.checkpoint(epoch), path)
-            return path
-        return None
+        if self.save_images_interval != 0 and epoch % self.save_images_interval == 0:
+            self.plot_sample_images(num_images=10, use_test_data=False)
+        return path
 
     def calculate_metrics(self, use_test_data=False):
         """models/segmentation_model.py:136-177: the binary mask metrics of the model's flood masks against the
@@ -610,6 +619,71 @@ class SegmentationModel:
             os.makedirs(os.path.dirname(path), exist_ok=True)
             df.to_csv(path)
         return df
+
+    # ---- pictures (models/segmentation_model.py:196-242) on floodgan.render
+
+    def plot_mask_image(self, path_to_image):
+        """models/segmentation_model.py:196-207: the predicted flood mask of one picture -- a PNG (bytes / 255, its
+        first three channels, as plt.imread) or a tile read_tile accepts -- as a "gray" image at
+        {data_path}/images/SegmentationMask_{name}_{time}.png.  The mask is decided on the device by the function
+        that decides fg_mask_confusion's.  Returns the path."""
+        import os
+        from datetime import datetime
+
+        from .png import read_image
+        from .render import save_image
+        image_name = path_to_image.split("/")[-1][:-4]
+        if path_to_image.lower().endswith(".png"):
+            a = read_image(path_to_image)
+            if a.shape[2] < 3:
+                raise ValueError(f"plot_mask_image: {path_to_image} has {a.shape[2]} channel(s); an RGB picture is needed")
+            a = a[:, :, :3].astype(np.float32) / np.float32(255)
+        else:
+            from .data import read_tile
+            a = read_tile(path_to_image)[:, :, :3]
+        x = torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))[None].to(self.device)
+        logits = self.model.logits_from_buf(unit_image_passthrough(x)[1])
+        now = str(datetime.now())[:-7].replace(" ", "-").replace(":", "-")
+        path = f"{self.data_path}/images/SegmentationMask_{image_name}_{now}.png"
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        if self.verbose:
+            print(f"Saving segmentation mask for '{image_name}' to {path}")
+        return save_image(path, logits, "mask_logits")
+
+    def plot_sample_images(self, num_images, use_test_data=False):
+        """models/segmentation_model.py:209-242: one sheet of the first num_images validation (or test) items, batch
+        element 0 of each: input (clip(x, 0, 1)) | true mask (t > 0.5) | predicted mask (sigmoid(logit) > 0.5), at
+        create_path("image"), under torch.manual_seed(self.seed).  Returns the path."""
+        import os
+
+        from .render import save_sheet
+        val_loader, test_loader = self.val_loader, self.test_loader
+        if val_loader is None and test_loader is None and self.data_path is not None:
+            _, val_loader, test_loader = self._loaders()
+        loader = test_loader if use_test_data else val_loader
+        if loader is None:
+            raise RuntimeError("no evaluation data: pass data_path or assign val_loader / test_loader")
+        xs, ts, ps, names = [], [], [], []
+        torch.manual_seed(self.seed)
+        for i, (input_image, true_mask, image_name) in enumerate(loader):
+            x = input_image.to(self.device)
+            t = true_mask.to(self.device)
+            logits = self.model.logits_from_buf(unit_image_passthrough(x)[1])
+            xs.append(x[:1])
+            ts.append(t[:1])
+            ps.append(logits.interior()[:1, :, :, 0])
+            names.append(image_name[0])
+            if i >= num_images - 1:
+                break
+        if not names:
+            raise RuntimeError("plot_sample_images: the loader is empty")
+        path = self.create_path("image")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        if self.verbose:
+            print("Saving sample images to", path)
+        self.last_panels = save_sheet(path, [("Input", "rgb_unit", xs), ("Ground Truth Mask", "mask_true", ts),
+                                             ("Predicted Mask", "mask_logits", ps)], names)
+        return path
 
     @staticmethod
     def tensor_to_mask(tensor, predicted=True):

@@ -643,6 +643,35 @@ int fg_lpips_layer(fg_view f0, fg_view f1, int c, const float* w, double* out, i
                    hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------- */
+/* pictures: predictions, attention and flood masks as RGBA8 (models/model.py:475-596,      */
+/* models/group.py:223-280, models/segmentation_model.py:196-242)                            */
+/* ---------------------------------------------------------------------------------------- */
+/* An RGBA8 canvas in device memory: pixel (row, col) at ptr[row * row_bytes + 4 * col], bytes R, G, B, A.
+ * ptr and row_bytes are multiples of 4; when both are multiples of 16 the kernels store 16 bytes per lane. */
+typedef struct fg_canvas {
+    unsigned char* ptr;
+    int height, width;
+    long long row_bytes;
+} fg_canvas;
+enum { FG_RENDER_SIGNED = 0, FG_RENDER_UNIT = 1 };
+enum { FG_SCALAR_UNIT = 0, FG_SCALAR_THRESHOLD = 1, FG_SCALAR_LOGIT = 2 };
+/* plt.imsave(path, img, vmin=0, vmax=1) of channels 0, 1, 2 of the strided [n, >= 3, h, w] view src, image i with
+ * its top-left corner at canvas (row0 + i step_rows, col0 + i step_cols).  FG_RENDER_SIGNED: v = clip((x + 1) * 0.5,
+ * 0, 1) (utils.tensor_to_numpy, models/utils.py:8-17); FG_RENDER_UNIT: v = clip(x, 0, 1) (the segmentation input,
+ * models/segmentation_model.py:227); byte = trunc(v * 255), every operation in fp32 and unfused; alpha 255; NaN
+ * gives byte 0.  Fails (FG_ERR_INVALID, nothing written) when a size is not positive, row_bytes < 4 width, or a
+ * panel would leave the canvas. */
+int fg_render_rgb(fg_sview src, int n, int h, int w, int mode, fg_canvas dst, int row0, int col0, int step_rows,
+                  int step_cols, hipStream_t stream);
+/* plt.imsave(path, img, vmin=0, vmax=1, cmap=...) of channel 0 of src through lut, the colormap's 256 RGBA
+ * entries (device, 4-byte aligned).  FG_SCALAR_UNIT: entry min(trunc(x * 256), 255) with the product in fp32, x < 0
+ * entry 0, NaN RGBA (0, 0, 0, 0); FG_SCALAR_THRESHOLD: entry 255 where x > 0.5, else entry 0 (tensor_to_mask(
+ * predicted=False), models/segmentation_model.py:247-248); FG_SCALAR_LOGIT: entry 255 where sigmoid(x) > 0.5 -- the
+ * device function that decides the masks of fg_mask_confusion -- else entry 0.  Placement and failures as above. */
+int fg_render_scalar(fg_sview src, int n, int h, int w, int mode, const unsigned char* lut, fg_canvas dst, int row0,
+                     int col0, int step_rows, int step_cols, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------- */
 /* tile data path                                                    */
 /* ---------------------------------------------------------------------------------------- */
 /* Host-side baseline TIFF decode, replacing tifffile.imread (models/data.py:64-68) for the files
