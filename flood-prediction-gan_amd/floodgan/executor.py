@@ -14,6 +14,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import opstate
 from . import plans as PL
 from ._lib import FG_ACT_LRELU, FG_ACT_NONE, FG_ACT_RELU, FG_PAD_REFLECT, FG_PAD_ZERO, require_device
 from .plans import Buf
@@ -549,9 +550,7 @@ def disc_prefix(buf, n):
     it bounds the prefix"""
     img = buf.t.numel() // buf.n
     v = Buf(buf.t[:n * img], n, buf.h, buf.w, buf.c, buf.pad)
-    slot = getattr(buf.t, "_fg_amax", None)
-    if slot is not None and getattr(buf.t, "_fg_amax_ver", None) == buf.t._version:
-        v.t._fg_amax, v.t._fg_amax_ver = slot, v.t._version
+    opstate.adopt(v, buf)
     return v
 
 

@@ -7,7 +7,8 @@ import os
 
 import torch
 
-from . import _lib as L
+from . import _lib as L, opstate
+from .opstate import adopt, is_presplit, is_splitpix, pack_slot, slot_of, tensor as _tensor, wrote  # noqa: F401
 from .plans import Buf, Slice, f3_wgrad_eligible, packed_numel, slab_numel, stem_wgrad_layout, wgrad_splits
 
 EPS = 1e-5
@@ -59,13 +60,10 @@ def wmap_struct(m):
 # ------------------------------------------------------------------ conv engine
 
 # ------------------------------------------------------------------ f16x3 operand scales
-#
-# The f16x3 conv math scales each operand by a power of two derived from a device scalar >=
-# max |operand|.  Those scalars live in slots of a zero-initialised pool (one fill per 4096
-# slots).  Producers that already touch every element (IN apply / backward) raise their
-# output's slot for free; otherwise the conv computes one with fg_absmax.  The slot is cached
-# on the tensor object and dropped by every op that writes that tensor (a stale slot is only
-# safe while it still bounds the contents).
+# The f16x3 conv math scales each operand by a power of two derived from a device scalar >= max |operand|.  Those
+# scalars live in slots of a zero-initialised pool (one fill per 4096 slots).  Producers that already touch every
+# element (IN apply / backward) raise their output's slot for free; otherwise the conv computes one with fg_absmax.
+# Slot, format and split copy are one versioned record on the tensor (opstate.py), dropped by every op that writes it.
 
 
 SHARDS = 64     # FG_AMAX_SHARDS: floats per absmax slot
@@ -85,25 +83,6 @@ class _SlotPool:
 
 
 _SLOTS = _SlotPool()
-
-
-def _tensor(obj):
-    return obj.t if isinstance(obj, (Buf, Slice)) else obj
-
-
-def _wrote(*objs):
-    """an op wrote these buffers: forget their cached absmax slots, split copies and pre-split format"""
-    for o in objs:
-        if o is not None:
-            t = _tensor(o)
-            if getattr(t, "_fg_amax", None) is not None:
-                t._fg_amax = None
-            if getattr(t, "_fg_split", None) is not None:
-                t._fg_split = None
-            if getattr(t, "_fg_presplit", False):
-                t._fg_presplit = False
-            if getattr(t, "_fg_splitpix", False):
-                t._fg_splitpix = False
 
 
 # Pre-split operands (FG_PRESPLIT, include/floodgan.h): the norm passes that feed a resblock conv write its
@@ -134,30 +113,6 @@ PRESPLIT_MAX_BYTES = (1 << 31) - (1 << 24)
 
 def presplit_fits(buf):
     return buf is not None and 4 * _tensor(buf).numel() <= PRESPLIT_MAX_BYTES
-
-
-def is_presplit(obj):
-    t = _tensor(obj)
-    if not getattr(t, "_fg_presplit", False):
-        return False
-    if getattr(t, "_fg_presplit_ver", None) != t._version:
-        raise RuntimeError("a pre-split (FG_PRESPLIT) buffer was written by torch since its producer ran")
-    return True
-
-
-def is_splitpix(obj):
-    """the buffer holds the fg_split_pixels layout written by its producer (in_apply(splitpix=True)), not fp32"""
-    t = _tensor(obj)
-    if not getattr(t, "_fg_splitpix", False):
-        return False
-    if getattr(t, "_fg_splitpix_ver", None) != t._version:
-        raise RuntimeError("a split-pixels buffer was written by torch since its producer ran")
-    return True
-
-
-def _mark_presplit(dst):
-    t = _tensor(dst)
-    t._fg_presplit, t._fg_presplit_ver = True, t._version
 
 
 # Self-checking scale caches (FLOODGAN_CHECK_SCALES=1, a debug mode: one device reduction and a host sync per
@@ -201,59 +156,39 @@ def check_scale(obj, slot, what):
 
 
 def absmax(t):
-    """Device scalar >= max |t| (the f16x3 operand-scale source), over the whole storage of a
-    tensor or of a Buf (border and padding channels included: everything a gather can read);
-    cached on the tensor until an op writes it."""
+    """Device scalar >= max |t| (the f16x3 operand-scale source), over the whole storage of a tensor, a parameter or
+    a Buf (border and padding channels included: everything a gather can read): the current slot (a producer's,
+    FusedAdam's, or an earlier call's), else a fresh fg_absmax pass (the only one kept) recorded on the tensor."""
     t = _tensor(t)
-    if getattr(t, "_fg_splitpix", False) and getattr(t, "_fg_splitpix_ver", None) == t._version:
-        raise RuntimeError("absmax of a split-pixels buffer (it holds fp16 pieces, read only by the window kernels)")
-    if getattr(t, "_fg_presplit", False) and getattr(t, "_fg_presplit_ver", None) == t._version:
-        # the producer's scale slot is the only valid scale source of a pre-split buffer
-        if getattr(t, "_fg_amax", None) is None or getattr(t, "_fg_amax_ver", None) != t._version:
+    st = opstate.current(t)
+    if st is not None:
+        if st.fmt == opstate.SPLITPIX:
+            raise RuntimeError("absmax of a split-pixels buffer (it holds fp16 pieces, read only by the window "
+                               "kernels)")
+        if st.slot is not None:
+            return st.slot
+        if st.fmt == opstate.PRESPLIT:      # the producer's scale slot is the only valid scale source
             raise RuntimeError("pre-split buffer without its producer's scale slot")
-        return t._fg_amax
-    cached = getattr(t, "_fg_amax", None)
-    # a slot is valid only together with the version counter it was recorded at: an in-place torch
-    # write since then (or a slot recorded without a version) means it may no longer bound t
-    if cached is not None and getattr(t, "_fg_amax_ver", None) == t._version:
-        return cached
-    out = _SLOTS.take(t.device)
-    L.check(_lib().fg_absmax(L.ptr(t), t.numel(), L.ptr(out), L.stream_handle()), "absmax")
-    t._fg_amax, t._fg_amax_ver = out, t._version
-    return out
+    slot = _SLOTS.take(t.device)
+    L.check(_lib().fg_absmax(L.ptr(t), t.numel(), L.ptr(slot), L.stream_handle()), "absmax")
+    opstate.record_slot(t, slot)
+    return slot
 
 
-def _amax_out(dst):
-    """slot for a producer to raise to max |dst| (f16x3 only), recorded on dst"""
-    _wrote(dst)
+def amax_slot(dst, fmt=opstate.FP32):
+    """a fresh slot for a producer (or several that share it) to raise to max |dst| (f16x3 only), recorded on dst"""
+    wrote(dst)
     if not L.fwd_f16x3() and not L.wgrad_f16x3():
         return None
     slot = _SLOTS.take(_dev(dst))
-    t = _tensor(dst)
-    # the kernel writes through a raw pointer (torch's counter does not move): record the version
-    # now, so a later in-place torch write invalidates the slot
-    t._fg_amax, t._fg_amax_ver = slot, t._version
+    opstate.record_slot(dst, slot, fmt)
     return slot
 
 
-def _weight_absmax(w):
-    """absmax slot of a parameter: the one FusedAdam's kernel raised with the last update while the
-    tensor's version counter shows no torch write since, else a fresh fg_absmax pass (recorded
-    with the version so the other packs of the same weights reuse it)"""
-    slot = getattr(w, "_fg_amax", None)
-    if slot is not None and getattr(w, "_fg_amax_ver", None) == w._version:
-        return slot
-    slot = _SLOTS.take(w.device)
-    L.check(_lib().fg_absmax(L.ptr(w), w.numel(), L.ptr(slot), L.stream_handle()), "absmax")
-    w._fg_amax, w._fg_amax_ver = slot, w._version
-    return slot
-
-
-# Pack cache (f16x3): each parameter keeps its packed layouts (one per weight map) with the absmax slot
-# they were scaled by; a pack is current while that slot is the parameter's current one (a torch write
-# moves the version counter, an adam_step installs a new slot AND re-packs every cached layout of the
-# parameters it updated in batched launches), so a training step packs nothing itself.
-# FLOODGAN_PACK_CACHE=0: pack at every use.
+# Pack cache (f16x3): each parameter keeps its packed layouts (opstate.packs, one per weight map); a pack is current
+# while the slot it was scaled by is the parameter's current one (a torch write makes that one stale, an adam_step
+# installs a new slot AND re-packs every cached layout of the parameters it updated in batched launches), so a
+# training step packs nothing itself.  FLOODGAN_PACK_CACHE=0: pack at every use.
 PACK_CACHE = os.environ.get("FLOODGAN_PACK_CACHE", "1") != "0"
 
 
@@ -261,15 +196,15 @@ def _repack(params):
     """re-pack every cached f16x3 layout of `params` with their current absmax slots (after an update)"""
     jobs = []
     for p in params:
-        packs = p.__dict__.get("_fg_packs")
+        packs = opstate.packs(p)
         if not packs:
             continue
-        slot = _weight_absmax(p)
-        for wp in packs.values():
+        slot = absmax(p)
+        for wp, wmap in packs.values():
             j = L.fg_pack_job()
-            j.w, j.w_absmax, j.dst, j.map = p.data_ptr(), slot.data_ptr(), wp.data_ptr(), wp._fg_map
+            j.w, j.w_absmax, j.dst, j.map = p.data_ptr(), slot.data_ptr(), wp.data_ptr(), wmap
             jobs.append(j)
-            wp.absmax = slot
+            opstate.record_slot(wp, slot)
     for i in range(0, len(jobs), L.FG_PACK_BATCH_MAX):
         part = jobs[i:i + L.FG_PACK_BATCH_MAX]
         arr = (L.fg_pack_job * len(part))(*part)
@@ -279,7 +214,7 @@ def _repack(params):
 def pack_weight(w, m, split=None):
     """Packed weight for the conv engine: fp32 [n][kh*jp]; or, by default under a split forward
     math, the pre-split layout -- bf16 h/m/l pieces (bf16x6, fg_pack_weight_split) or scaled fp16
-    h/l pieces (f16x3, fg_pack_weight_f16; the tensor carries its scale source as `.absmax`).
+    h/l pieces (f16x3, fg_pack_weight_f16; opstate.pack_slot gives its scale source).
     Conv problems built on it carry w_split = 1 or 2 accordingly."""
     L.require_device(w, "weight")
     w = w.contiguous()
@@ -289,22 +224,21 @@ def pack_weight(w, m, split=None):
     elif split is True:
         split = "f16x3" if L.fwd_f16x3() else "bf16x6"
     if split == "f16x3":
-        amax = _weight_absmax(w)
-        packs = w.__dict__.setdefault("_fg_packs", {}) if PACK_CACHE else None
+        amax = absmax(w)
+        packs = opstate.packs(w) if PACK_CACHE else None
         key = bytes(s)
-        if packs is not None and key in packs and packs[key].absmax is amax:
+        if packs is not None and key in packs and pack_slot(packs[key][0]) is amax:
             if CHECK_SCALES:
-                _check_pack(w, s, amax, packs[key])
-            return packs[key]          # packed from the current values (re-packed by the last adam_step)
+                _check_pack(w, s, amax, packs[key][0])
+            return packs[key][0]       # packed from the current values (re-packed by the last adam_step)
         if CHECK_SCALES:
             check_scale(w, amax, "weight")
         wp = torch.empty(2 * packed_numel(m), dtype=torch.float16, device=w.device)
         L.check(_lib().fg_pack_weight_f16(L.ptr(w), C.byref(s), L.ptr(amax), L.ptr(wp), L.stream_handle()),
                 "pack_weight_f16")
-        wp.absmax = amax
+        opstate.record_slot(wp, amax)
         if packs is not None:
-            wp._fg_map = s
-            packs[key] = wp
+            packs[key] = (wp, s)
         return wp
     if split == "bf16x6":
         wp = torch.empty(3 * packed_numel(m), dtype=torch.bfloat16, device=w.device)
@@ -455,13 +389,7 @@ def _conv(probs, in_stats=False, tag=None):
             s.x_absmax = keep[id(xb)].data_ptr()
             if CHECK_SCALES:
                 check_scale(xb, keep[id(xb)], "conv input")
-            wa = getattr(wt, "absmax", None)
-            if wa is None:              # fp32 weights split on the fly: scale from their own max
-                if ("w", id(wt)) not in keep:
-                    keep[("w", id(wt))] = _SLOTS.take(wt.device)
-                    L.check(_lib().fg_absmax(L.ptr(wt), wt.numel(), L.ptr(keep[("w", id(wt))]),
-                                             L.stream_handle()), "absmax")
-                wa = keep[("w", id(wt))]
+            wa = pack_slot(wt) if s.w_split == 2 else absmax(wt)    # (fp32 weights, split on the fly: their own max)
             s.w_absmax = wa.data_ptr()
             if CHECK_SCALES and wt.dtype == torch.float32:
                 check_scale(wt, wa, "fp32 weight")
@@ -469,7 +397,7 @@ def _conv(probs, in_stats=False, tag=None):
     _timed(tag, lambda: L.check(_lib().fg_conv_fwd(arr, len(probs), L.stream_handle()), "conv_fwd"))
     global LAST_CONV_KERNEL
     LAST_CONV_KERNEL = L.last_launch()
-    _wrote(*[p["y"][0] for p in probs])
+    wrote(*[p["y"][0] for p in probs])
     return stats
 
 
@@ -515,35 +443,34 @@ def _stats_partials(probs, arr):
 
 
 def split_pixels(X):
-    """fg_split_pixels copy of a Buf (32 or 64 channels): fp16 h/l pieces of the scaled values,
-    the window-conv operand.  Cached on the buffer's tensor until an op writes it."""
+    """(fg_split_pixels copy of a Buf (32 or 64 channels): fp16 h/l pieces of the scaled values, the window-conv
+    operand; the slot it was scaled by), cached on the buffer's tensor until an op writes it"""
     t = X.t
-    if is_presplit(X):
+    st = opstate.current(t)
+    if st is not None and st.fmt == opstate.PRESPLIT:
         raise RuntimeError("split_pixels of a pre-split buffer")
-    if is_splitpix(X):
-        return t._fg_split              # the producer wrote the split layout itself (in_apply(splitpix=True))
-    cached = getattr(t, "_fg_split", None)
-    if cached is not None and getattr(t, "_fg_split_ver", None) == t._version:
-        if CHECK_SCALES:
-            check_scale(X, cached.absmax, "split-copy source")
-            if cached.absmax is not absmax(t):
+    cached = None if st is None else st.split
+    if cached is not None:
+        if CHECK_SCALES and st.fmt != opstate.SPLITPIX:     # (split-pixels: its producer wrote the layout itself)
+            check_scale(X, cached[1], "split-copy source")
+            if cached[1] is not absmax(t):
                 raise RuntimeError("FLOODGAN_CHECK_SCALES: a cached split copy was scaled by another slot")
-            fresh = torch.empty_like(cached)
-            L.check(_lib().fg_split_pixels(L.ptr(t), X.n * X.hp * X.wp, X.c, X.wp, L.ptr(cached.absmax), L.ptr(fresh),
+            fresh = torch.empty_like(cached[0])
+            L.check(_lib().fg_split_pixels(L.ptr(t), X.n * X.hp * X.wp, X.c, X.wp, L.ptr(cached[1]), L.ptr(fresh),
                                            L.stream_handle()), "split_pixels")
-            if not torch.equal(fresh.view(torch.int16), cached.view(torch.int16)):
+            if not torch.equal(fresh.view(torch.int16), cached[0].view(torch.int16)):
                 raise RuntimeError("FLOODGAN_CHECK_SCALES: a cached split copy differs from its source")
             _count_check("split_copy")
         return cached
     npix = X.n * X.hp * X.wp
     out = torch.empty(npix * 2 * X.c, dtype=torch.float16, device=t.device)
+    slot = absmax(t)
     if CHECK_SCALES:
-        check_scale(X, absmax(t), "split-copy source")
-    L.check(_lib().fg_split_pixels(L.ptr(t), npix, X.c, X.wp, L.ptr(absmax(t)), L.ptr(out), L.stream_handle()),
+        check_scale(X, slot, "split-copy source")
+    L.check(_lib().fg_split_pixels(L.ptr(t), npix, X.c, X.wp, L.ptr(slot), L.ptr(out), L.stream_handle()),
             "split_pixels")
-    out.absmax = absmax(t)
-    t._fg_split, t._fg_split_ver = out, t._version
-    return out
+    opstate.record_slot(t, slot, split=(out, slot))
+    return out, slot
 
 
 def win_eligible(prob):
@@ -564,7 +491,7 @@ def win_eligible(prob):
 def conv_win(prob, tag=None):
     """The row-strip window conv (fg_conv_win) of one plans.conv_problem."""
     X, off = prob["x"]
-    xs = split_pixels(X)
+    xs, x_slot = split_pixels(X)
     arr = (L.fg_conv_problem * 1)()
     s = arr[0]
     s.x, s.w, s.y = _addr(prob["x"]), _addr(prob["w"]), _addr(prob["y"])
@@ -572,11 +499,10 @@ def conv_win(prob, tag=None):
     s.bias = prob["bias"].data_ptr() if prob["bias"] is not None else None
     for k in _CONV_FIELDS:
         setattr(s, k, int(prob[k]))
-    s.x_absmax = xs.absmax.data_ptr()
-    s.w_absmax = prob["w"][0].absmax.data_ptr()
-
+    s.x_absmax = x_slot.data_ptr()
+    s.w_absmax = pack_slot(prob["w"][0]).data_ptr()
     _timed(tag, lambda: L.check(_lib().fg_conv_win(arr, L.ptr(xs), off // X.c, L.stream_handle()), "conv_win"))
-    _wrote(prob["y"][0])
+    wrote(prob["y"][0])
 
 
 WIN_WGRAD_SPLITS = 216   # x 7 kernel rows = 1512 workgroups of 4 waves (several resident per CU); a multiple of 8:
@@ -598,14 +524,14 @@ def wgrad_win_eligible(prob):
 def _wgrad_win(prob, wmap, dw, accumulate):
     P, poff = prob["p"]
     X, xoff = prob["x"]
-    ps, xs = split_pixels(P), split_pixels(X)
+    (ps, p_slot), (xs, x_slot) = split_pixels(P), split_pixels(X)
     prob = dict(prob, splits=WIN_WGRAD_SPLITS, m_chunk=1)
     slab = torch.empty(slab_numel(prob), dtype=torch.float32, device=P.t.device)
     s = L.fg_wgrad_problem()
     s.p, s.x, s.out = _addr(prob["p"]), _addr(prob["x"]), slab.data_ptr()
     for k in _WG_FIELDS:
         setattr(s, k, int(prob[k]))
-    s.p_absmax, s.x_absmax = ps.absmax.data_ptr(), xs.absmax.data_ptr()
+    s.p_absmax, s.x_absmax = p_slot.data_ptr(), x_slot.data_ptr()
     st = L.stream_handle()
     p_pix0 = poff // P.c
     L.check(_lib().fg_conv_wgrad_win(C.byref(s), L.ptr(ps), p_pix0, p_pix0 % P.wp, P.wp, L.ptr(xs), xoff // X.c,
@@ -677,7 +603,7 @@ N1_ROWS = 5   # input rows per weight-gradient block
 
 def conv_n1_fwd(X, w, b, y):
     """model.11 forward: X Buf (512 ch, border 1), w (1, 512, 4, 4), y [N, 1, h-1, w-1] contiguous"""
-    _wrote(y)
+    wrote(y)
     L.check(_lib().fg_conv_n1_fwd(L.ptr(X.t), X.n, X.hp, X.wp, X.c, L.ptr(w.contiguous()), L.ptr(b), L.ptr(y),
                                   y.shape[2], y.shape[3], L.stream_handle()), "conv_n1_fwd")
 
@@ -701,7 +627,7 @@ def d0_input_grad(G, w, c0, cn, y, accumulate):
     """dL/d(D input channels c0 .. c0+cn-1) of model.0 (4x4 s2 p1, 64 outputs) from its output gradient G (Buf, 64 ch,
     zero border >= 1) into y [N, >= cn, H, W] contiguous NCHW channels 0 .. cn-1 (fg_d0_input_grad, exact fp32)"""
     assert y.is_contiguous() and w.is_contiguous()
-    _wrote(y)
+    wrote(y)
     L.check(_lib().fg_d0_input_grad(view(G), L.ptr(w), w.shape[1], c0, cn, L.ptr(y), y.shape[1], y.shape[2],
                                     y.shape[3], int(accumulate), L.stream_handle()), "d0_input_grad")
 
@@ -713,38 +639,28 @@ def pack_input(a, ca, b, cb, dst, img0, nimg, pad_mode, amax=None):
     of all of dst's images takes a fresh one; packs that fill dst in parts pass the slot they share
     (amax_slot(dst), taken before the first part)."""
     if amax is None:
-        full = img0 == 0 and nimg == dst.n
-        slot = _amax_out(dst) if full else None
-        if slot is None:
-            _wrote(dst)
+        wrote(dst)
+        slot = amax_slot(dst) if img0 == 0 and nimg == dst.n else None
     else:
         # a part of a multi-launch fill: the slot must be the one amax_slot(dst) recorded on dst, at dst's
         # current version (the kernels write through raw pointers, so the counter has not moved since)
         slot = amax
-        t = _tensor(dst)
-        if getattr(t, "_fg_amax", None) is not amax or getattr(t, "_fg_amax_ver", None) != t._version:
+        if opstate.keep_slot_across(dst) is not amax:
             raise RuntimeError("pack_input: the shared absmax slot is not the one amax_slot(dst) recorded on dst "
                                "(or dst was written by torch since)")
-        t._fg_split = None
-        t._fg_presplit = False
     L.check(_lib().fg_pack_input(sview(a), ca, sview(b), cb, view(dst), img0, nimg, pad_mode, L.ptr(slot),
                                  L.stream_handle()), "pack_input")
-
-
-def amax_slot(dst):
-    """a fresh absmax slot recorded on dst, for producers that write dst in several launches"""
-    return _amax_out(dst)
 
 
 def conv1x1_fwd(X, w, b, n_out, Y):
     """the attention head's 1x1 conv (fp32 FMA, fg_conv1x1_fwd): Y[..., :n_out] = w X + b, Y's other
     channels 0"""
-    _wrote(Y)
+    wrote(Y)
     L.check(_lib().fg_conv1x1_fwd(view(X), L.ptr(w), L.ptr(b), n_out, view(Y), L.stream_handle()), "conv1x1_fwd")
 
 
 def conv1x1_dgrad(GY, w, n_out, GX):
-    _wrote(GX)
+    wrote(GX)
     L.check(_lib().fg_conv1x1_dgrad(view(GY), L.ptr(w), n_out, view(GX), L.stream_handle()), "conv1x1_dgrad")
 
 
@@ -755,19 +671,19 @@ def conv1x1_wgrad(GY, X, n_out, dw, db, accumulate=False):
 
 
 def zero_border(B):
-    _wrote(B)
+    wrote(B)
     L.check(_lib().fg_zero_border(view(B), L.stream_handle()), "zero_border")
 
 
 def fold_add(gpad, fold_pad, add, dst):
-    _wrote(dst)
+    wrote(dst)
     L.check(_lib().fg_fold_add(view(gpad), fold_pad, view(add), view(dst), L.stream_handle()), "fold_add")
 
 
 def unfold_nchw(gpad, fold_pad, c, dst, acc_channels=0):
     """dst [N, c', H, W] (any strides): channels < c get the reflect-pad adjoint of gpad (accumulated for
     channels < acc_channels)"""
-    _wrote(dst)
+    wrote(dst)
     N, _, H, W = dst.shape
     assert gpad.n == N and dst.shape[1] >= c
     L.check(_lib().fg_unfold_nchw(view(gpad), fold_pad, c, sview(dst), H, W, acc_channels, L.stream_handle()),
@@ -795,35 +711,29 @@ def in_apply(src, mean, rstd, act, residual, dst, pad_mode, presplit=False, ps_c
     in the fg_split_pixels layout the window kernels read (split_pixels(dst) then returns it; no fp32 values)"""
     if splitpix:
         assert residual is None and not presplit and ps_copy is None and L.fwd_f16x3() and L.wgrad_f16x3()
-        slot = _amax_out(dst)
+        slot = amax_slot(dst)
         L.check(_lib().fg_in_apply_splitpix(view(src), L.ptr(mean), L.ptr(rstd), act, view(dst), pad_mode,
                                             L.ptr(slot), L.stream_handle()), "in_apply_splitpix")
-        t = _tensor(dst)
-        split = t.view(torch.float16)
-        split.absmax = slot
-        t._fg_split, t._fg_split_ver = split, t._version
-        t._fg_splitpix, t._fg_splitpix_ver = True, t._version
+        opstate.record_slot(dst, slot, opstate.SPLITPIX, split=(_tensor(dst).view(torch.float16), slot))
         return
     presplit = presplit and presplit_fits(dst)
     if ps_copy is not None:
         assert presplit_fits(ps_copy), "pre-split copy beyond PRESPLIT_MAX_BYTES (the caller checks presplit_fits)"
         assert not presplit and L.fwd_f16x3()
         ra = absmax(residual) if residual is not None else None
-        slot, ps_slot = _amax_out(dst), _amax_out(ps_copy)
+        slot, ps_slot = amax_slot(dst), amax_slot(ps_copy, opstate.PRESPLIT)
         L.check(_lib().fg_in_apply_dual(view(src), L.ptr(mean), L.ptr(rstd), act, view(residual), L.ptr(ra), view(dst),
                                         pad_mode, L.ptr(slot), L.ptr(ps_copy.t), L.ptr(ps_slot), L.stream_handle()),
                 "in_apply_dual")
-        _mark_presplit(ps_copy)
         return
     if presplit:
         assert residual is None and L.fwd_f16x3()
-        slot = _amax_out(dst)
         L.check(_lib().fg_in_apply_presplit(view(src), L.ptr(mean), L.ptr(rstd), act, view(dst), pad_mode,
-                                            L.ptr(slot), L.stream_handle()), "in_apply_presplit")
-        _mark_presplit(dst)
+                                            L.ptr(amax_slot(dst, opstate.PRESPLIT)), L.stream_handle()),
+                "in_apply_presplit")
         return
     L.check(_lib().fg_in_apply(view(src), L.ptr(mean), L.ptr(rstd), act, view(residual), view(dst), pad_mode,
-                               L.ptr(_amax_out(dst)), L.stream_handle()), "in_apply")
+                               L.ptr(amax_slot(dst)), L.stream_handle()), "in_apply")
 
 
 def in_bwd(gsrc, fold_pad, gadd, src, mean, rstd, act, dst, bias_grad=None, bias_accumulate=False, gsum=None,
@@ -832,31 +742,24 @@ def in_bwd(gsrc, fold_pad, gadd, src, mean, rstd, act, dst, bias_grad=None, bias
     receives the gathered gradient fold(gsrc) + gadd (written by the statistics pass that reads it anyway).
     presplit: dst is written in the FG_PRESPLIT format (the f16x3 math)."""
     work = _work(src.n, src.c, src.t.device)
-    _wrote(gsum)
-    if presplit and presplit_fits(dst):
-        assert L.fwd_f16x3()
-        slot = _amax_out(dst)
-        L.check(_lib().fg_in_bwd_presplit(view(gsrc), fold_pad, view(gadd), view(src), L.ptr(mean), L.ptr(rstd), act,
-                                          view(dst), L.ptr(bias_grad), int(bias_accumulate), view(gsum), L.ptr(work),
-                                          L.ptr(slot), L.stream_handle()), "in_bwd_presplit")
-        _mark_presplit(dst)
-        return
-    L.check(_lib().fg_in_bwd(view(gsrc), fold_pad, view(gadd), view(src), L.ptr(mean), L.ptr(rstd), act, view(dst),
-                             L.ptr(bias_grad), int(bias_accumulate), view(gsum), L.ptr(work),
-                             L.ptr(_amax_out(dst)), L.stream_handle()), "in_bwd")
+    wrote(gsum)
+    presplit = presplit and presplit_fits(dst)
+    assert not presplit or L.fwd_f16x3()
+    fn, fmt = (_lib().fg_in_bwd_presplit, opstate.PRESPLIT) if presplit else (_lib().fg_in_bwd, opstate.FP32)
+    L.check(fn(view(gsrc), fold_pad, view(gadd), view(src), L.ptr(mean), L.ptr(rstd), act, view(dst),
+               L.ptr(bias_grad), int(bias_accumulate), view(gsum), L.ptr(work), L.ptr(amax_slot(dst, fmt)),
+               L.stream_handle()), "in_bwd_presplit" if presplit else "in_bwd")
 
 
 def in_apply_head(src, mean, rstd, act, dst, pad_mode, w, b, n_out, Y):
     """fg_in_apply_head: dst = act(IN(src)) (fp32, unpadded; absmax slot raised) AND the attention head's 1x1 logits
     Y[..., :n_out] = w dst + b (Y's other channels 0), bit-identical to in_apply + conv1x1_fwd.  dst None: only the
     logits (the fused backward, in_bwd_head with wgrad, recomputes the activation)"""
+    wrote(Y)
     if dst is None:
-        _wrote(Y)
-        dv = L.fg_view(None, src.n, src.h, src.w, src.c, 0)
-        amax = None
+        dv, amax = L.fg_view(None, src.n, src.h, src.w, src.c, 0), None
     else:
-        _wrote(dst, Y)
-        dv, amax = view(dst), L.ptr(_amax_out(dst))
+        dv, amax = view(dst), L.ptr(amax_slot(dst))
     L.check(_lib().fg_in_apply_head(view(src), L.ptr(mean), L.ptr(rstd), act, dv, pad_mode, amax,
                                     L.ptr(w.contiguous()), L.ptr(b), n_out, view(Y), L.stream_handle()),
             "in_apply_head")
@@ -875,34 +778,20 @@ def in_bwd_head(GY, w, n_out, src, mean, rstd, act, dst, bias_grad=None, bias_ac
         dw, db, acc = wgrad
         nf = int(_lib().fg_in_head_wgrad_workspace_floats(src.n, src.h, src.w, n_out))
         wg_work = torch.empty(nf, dtype=torch.float32, device=src.t.device)
-    tail = (L.ptr(dw), L.ptr(db), int(acc), L.ptr(wg_work), L.stream_handle())
-    if presplit and presplit_fits(dst):
-        assert L.fwd_f16x3()
-        slot = _amax_out(dst)
-        L.check(_lib().fg_in_bwd_head(view(GY), L.ptr(w.contiguous()), n_out, view(src), L.ptr(mean), L.ptr(rstd), act,
-                                      view(dst), L.ptr(bias_grad), int(bias_accumulate), L.ptr(work), None, L.ptr(slot),
-                                      *tail), "in_bwd_head")
-        _mark_presplit(dst)
-        return
-    _wrote(dst)
+    presplit = presplit and presplit_fits(dst)
+    assert not presplit or L.fwd_f16x3()
+    slot = L.ptr(amax_slot(dst, opstate.PRESPLIT if presplit else opstate.FP32))
+    slots = (None, slot) if presplit else (slot, None)      # (fp32 dst's slot, pre-split dst's slot)
     L.check(_lib().fg_in_bwd_head(view(GY), L.ptr(w.contiguous()), n_out, view(src), L.ptr(mean), L.ptr(rstd), act,
-                                  view(dst), L.ptr(bias_grad), int(bias_accumulate), L.ptr(work),
-                                  L.ptr(_amax_out(dst)), None, *tail), "in_bwd_head")
+                                  view(dst), L.ptr(bias_grad), int(bias_accumulate), L.ptr(work), *slots,
+                                  L.ptr(dw), L.ptr(db), int(acc), L.ptr(wg_work), L.stream_handle()), "in_bwd_head")
 
 
 def act_bwd(g, y, act, border_zero=False):
     # in place g *= act'(y) with act' in {0, 0.2, 1}: |g| cannot grow, so a cached absmax slot still
     # bounds it and is kept; a cached pre-split copy no longer matches the contents and is dropped.  Without a
     # cached slot, border_zero=True (g's border holds zeros) lets the kernel raise a fresh one over the interior.
-    t = _tensor(g)
-    slot, ver = getattr(t, "_fg_amax", None), getattr(t, "_fg_amax_ver", None)
-    valid = slot is not None and ver == t._version
-    _wrote(g)
-    raise_slot = None
-    if valid:
-        t._fg_amax, t._fg_amax_ver = slot, ver
-    elif border_zero:
-        raise_slot = _amax_out(g)
+    raise_slot = amax_slot(g) if opstate.keep_slot_across(g) is None and border_zero else None
     L.check(_lib().fg_act_bwd(view(g), view(y), act, L.ptr(raise_slot), L.stream_handle()), "act_bwd")
 
 
@@ -923,16 +812,14 @@ def _bn_work(n, c, dev):
 
 def _dst_slot(dst, slot):
     """absmax slot a producer raises for dst: the caller's (a buffer several producers write in
-    channel slices shares one slot, taken once with _amax_out(buffer)), else a fresh one for a whole
+    channel slices shares one slot, taken once with amax_slot(buffer)), else a fresh one for a whole
     Buf; a Slice without a slot only invalidates its buffer's caches"""
     if dst is None:
         return None
-    if slot is not None:
-        return slot
-    if isinstance(dst, Slice):
-        _wrote(dst)
-        return None
-    return _amax_out(dst)
+    if slot is None:
+        wrote(dst)
+        slot = None if isinstance(dst, Slice) else amax_slot(dst)
+    return slot
 
 
 def bn_stats(src, groups=1, running=None, eps=EPS, momentum=BN_MOMENTUM):
@@ -1000,7 +887,7 @@ def dropout_mask(seed, shape, device):
 
 
 def maxpool2(src, dst):
-    _wrote(dst)
+    wrote(dst)
     L.check(_lib().fg_maxpool2(view(src), view(dst), L.stream_handle()), "maxpool2")
 
 
@@ -1013,7 +900,7 @@ def maxpool2_bwd(src, g_pooled, g_src, choice=None):
                 or not choice.is_contiguous() or choice.device != src.t.device:
             raise RuntimeError(f"maxpool2_bwd: choice must be a contiguous uint8 tensor of shape {want} on the "
                                f"source Buf's device (got {choice.dtype} {tuple(choice.shape)})")
-    _wrote(g_src)
+    wrote(g_src)
     L.check(_lib().fg_maxpool2_bwd(view(src), view(g_pooled), view(g_src), L.ptr(choice), L.stream_handle()),
             "maxpool2_bwd")
 
@@ -1029,7 +916,7 @@ def bce_logits(logits, target, gscale, grad, loss_out, correct_out=None):
     assert isinstance(grad, Buf) and loss_out.dtype == torch.float32
     assert correct_out is None or correct_out.dtype == torch.int64
     work = torch.empty(int(_lib().fg_bce_logits_workspace_doubles()), dtype=torch.float64, device=target.device)
-    _wrote(grad)
+    wrote(grad)
     L.check(_lib().fg_bce_logits(view(logits), L.ptr(target), C.c_float(gscale), view(grad), L.ptr(loss_out),
                                  L.ptr(correct_out), L.ptr(work), L.stream_handle()), "bce_logits")
 
@@ -1044,14 +931,14 @@ def lpips_stem(x, wt, bias, Y, img0=0):
     if Cc != 3 or tuple(wt.shape) != (3, 11, 11, 64) or not wt.is_contiguous() or bias.numel() != 64:
         raise RuntimeError(f"lpips_stem: a 3-channel image and a [3, 11, 11, 64] weight (got {tuple(x.shape)}, "
                            f"{tuple(wt.shape)})")
-    _wrote(Y)
+    wrote(Y)
     L.check(_lib().fg_lpips_stem(sview(x), N, H, W, L.ptr(wt), L.ptr(bias), view(Y), img0, L.stream_handle()),
             "lpips_stem")
 
 
 def maxpool3s2(src, dst):
     """nn.MaxPool2d(3, 2) of src's interior into dst's interior (dst's border is left as it is)"""
-    _wrote(dst)
+    wrote(dst)
     L.check(_lib().fg_maxpool3s2(view(src), view(dst), L.stream_handle()), "maxpool3s2")
 
 
@@ -1079,26 +966,26 @@ def lpips_layer(f0, f1, c, w, out, accumulate=False):
 # ------------------------------------------------------------------ tail / losses / adam
 
 def tail_fwd(cl, al, x, out, mask):
-    _wrote(out, mask)
+    wrote(out, mask)
     L.check(_lib().fg_tail_fwd(view(cl), view(al), sview(x), L.ptr(out), L.ptr(mask), L.stream_handle()), "tail_fwd")
 
 
 def tail_bwd(cl, al, x, g_out, gc, ga, gx=None, g_mask=None):
     """gx (optional [N, C, H, W] tensor): channels 0..2 receive the background term's input gradient;
     g_mask (optional [N, H, W]): dL/d(last_attention_mask), added to attention channel 9's gradient"""
-    _wrote(gx)
+    wrote(gx)
     gm = None if g_mask is None else g_mask.unsqueeze(1)
     L.check(_lib().fg_tail_bwd(view(cl), view(al), sview(x), sview(g_out), sview(gm), view(gc), view(ga), sview(gx),
-                               L.ptr(_amax_out(gc)), L.ptr(_amax_out(ga)), L.stream_handle()), "tail_bwd")
+                               L.ptr(amax_slot(gc)), L.ptr(amax_slot(ga)), L.stream_handle()), "tail_bwd")
 
 
 def tanh_head_fwd(logits, c, out):
-    _wrote(out)
+    wrote(out)
     L.check(_lib().fg_tanh_head_fwd(view(logits), c, sview(out), L.stream_handle()), "tanh_head_fwd")
 
 
 def tanh_head_bwd(logits, c, g_out, g_logits):
-    _wrote(g_logits)
+    wrote(g_logits)
     L.check(_lib().fg_tanh_head_bwd(view(logits), c, sview(g_out), view(g_logits), L.stream_handle()),
             "tanh_head_bwd")
 
@@ -1106,7 +993,7 @@ def tanh_head_bwd(logits, c, g_out, g_logits):
 def mse_const(p, target, gscale, loss_out, g=None):
     """loss_out[0] = mean((p - target)^2); g = gscale * dL/dp (optional)"""
     work = torch.empty(1024, dtype=torch.float64, device=p.device)
-    _wrote(g)
+    wrote(g)
     L.check(_lib().fg_mse_const(L.ptr(p), p.numel(), C.c_float(target), C.c_float(gscale), L.ptr(loss_out),
                                 L.ptr(g), L.ptr(work), L.stream_handle()), "mse")
 
@@ -1115,7 +1002,7 @@ def l1(a, b, gscale, loss_out, g=None, accumulate=False, loss_scale=1.0):
     """loss_out[0] = loss_scale * mean|a - b| over [N,C,H,W]; g (contiguous NCHW) = gscale * dL/da"""
     N, Cc, H, W = a.shape
     work = torch.empty(1024, dtype=torch.float64, device=a.device)
-    _wrote(g)
+    wrote(g)
     L.check(_lib().fg_l1(sview(a), sview(b), N, Cc, H, W, C.c_float(gscale), C.c_float(loss_scale), L.ptr(loss_out),
                          L.ptr(g),
                          int(accumulate), L.ptr(work), L.stream_handle()), "l1")
@@ -1141,9 +1028,8 @@ def adam_step(entries, lr, beta1, beta2, eps, step):
     L.check(_lib().fg_adam_step(arr, len(entries), float(lr), float(beta1), float(beta2), float(eps), int(step),
                                 L.stream_handle()), "adam_step")
     for (p, _, _, _), slot in zip(entries, slots):
-        # the kernel wrote p through a raw pointer: torch's version counter did not move, so a
-        # later in-place torch write (another optimizer, load_state_dict) still invalidates this
-        p._fg_amax, p._fg_amax_ver = slot, p._version
+        # (stamped now: a later in-place torch write, another optimizer's or load_state_dict's, invalidates it)
+        opstate.record_slot(p, slot)
     if slots and slots[0] is not None and PACK_CACHE:
         _repack([e[0] for e in entries])
 

@@ -232,7 +232,7 @@ def gen_forward(P, B, x, masks=None, training=True, save=True):
                 mean, invstd = _stats(B, nm["downnorm"], c, 1, training)
             nxt = Buf.zeros(N, h, w, inner, 1, dev)
             cat = Buf.zeros(N, h, w, 2 * inner, 1, dev)
-            slot = ops._amax_out(cat)                 # one operand-scale slot, raised by both halves' producers
+            slot = ops.amax_slot(cat)               # one operand-scale slot, raised by both halves' producers
             gam = P.get(nm.get("downnorm", "") + ".weight")
             bet = P.get(nm.get("downnorm", "") + ".bias")
             ops.bn_apply(c, 1, mean, invstd, gam, bet, None, FG_ACT_LRELU, nxt, FG_ACT_RELU, Slice(cat, 0, inner),

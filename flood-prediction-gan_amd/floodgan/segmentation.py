@@ -255,7 +255,7 @@ def unit_image(x, buf=None, nchw=True):
     from . import _lib as L
     L.check(L.load().fg_unit_image(ops.sview(x), N, C, H, W, L.ptr(out), ops.view(buf), L.stream_handle()),
             "unit_image")
-    ops._wrote(buf)
+    ops.wrote(buf)
     return out, buf
 
 

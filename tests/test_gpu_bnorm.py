@@ -391,15 +391,15 @@ def test_bn_absmax_slots(f16x3, n, c, h, w):
     torch.cuda.synchronize()
     m0, m1 = float(d0.t.abs().max()), float(wide.interior()[..., c:].abs().max())
     assert m1 > 2 * m0 > 0                                                # the data does separate the two
-    assert float(d0.t._fg_amax.max()) == m0
-    assert wide.t._fg_amax is slot and float(slot.max()) == m1
+    assert float(ops.slot_of(d0).max()) == m0
+    assert ops.slot_of(wide) is slot and float(slot.max()) == m1
     assert bool(torch.isnan(wide.interior()[..., :c]).all())
 
     dst = nan_buf(n, h, w, c, 0)
     ops.bn_bwd(buf_from(f32(n, c, h, w, g=g), 0, "constant"), L.FG_ACT_RELU, None, 0, src, 1, mean, invstd, gamma,
                beta, None, dst)
     torch.cuda.synchronize()
-    assert float(dst.t._fg_amax.max()) == float(dst.t.abs().max()) > 0
+    assert float(ops.slot_of(dst).max()) == float(dst.t.abs().max()) > 0
 
 
 @pytest.mark.parametrize("h,w", [(16, 16), (7, 9), (2, 2)])

@@ -151,7 +151,7 @@ def test_pack_input_absmax_slot(f16x3, c_alloc, h, w):
         dst = nan_buf(2, h, w, c_alloc, 2)
         ops.pack_input(a.to(DEV), 3, b.to(DEV), 6, dst, 0, 2, mode)
         torch.cuda.synchronize()
-        assert float(dst.t._fg_amax.max()) == float(dst.t.abs().max()) == 77.0
+        assert float(ops.slot_of(dst).max()) == float(dst.t.abs().max()) == 77.0
 
 
 # ------------------------------------------------------------------ fg_zero_border

@@ -130,7 +130,7 @@ def test_adam_tensor_layout(conv_math, init, report):
         worst = trio.check(f"layout/{conv_math}/{init}/step{step + 1}")
     report("adam_tensor_layout", conv_math=conv_math, init=init, **worst)
     for i, p in enumerate(trio.dev):
-        slot = getattr(p, "_fg_amax", None)
+        slot = ops.slot_of(p)
         if conv_math != "f16x3":
             assert slot is None
             continue
