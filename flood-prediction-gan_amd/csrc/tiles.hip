@@ -237,6 +237,101 @@ __global__ void tile_vpass_kernel(const fg_tile_batch B, int rows) {
     }
 }
 
+// ------------------------------------------------------------------------------------------ mask tiles
+//
+// fg_mask_tile_batch: the segmentation tiles' np.fliplr + HWC -> CHW (models/data.py:187-198), a pure copy.  Pure
+// streaming, grid-stride, no LDS, no arithmetic on the values.  A pixel is 12 bytes, so a lane per pixel moves
+// 12-byte pieces at a 12-byte pitch; the wide kernel instead gives a lane one aligned 16-byte run of a DESTINATION
+// row (render.hip's shape), so consecutive lanes store consecutive 16 bytes (1 KiB per wave instruction):
+//   * image, channels-last destination: a row is 3w contiguous floats on both sides.  Unflipped, the run's source
+//     is the same 16 bytes of the raw row (one 16-byte load).  Flipped, the pixels of the row are reversed while
+//     each keeps its channel order, so the run's four floats come from two neighbouring source pixels: four 4-byte
+//     loads, which over a wave still cover one contiguous (descending) 1 KiB of the raw row;
+//   * mask: the mirrored run is the aligned run at w - 4 - x0 with its four floats reversed (one 16-byte load).
+// A row of w pixels is 3w/4 image runs + w/4 mask runs = w lanes, so one launch of n*h*w lanes does both; at the
+// tiles' 1024 columns the 12 image waves and 4 mask waves of a row are each uniform.
+// The flip choice arrives as a bit mask in the kernel arguments: no per-batch device array.
+
+struct MaskGeo {
+    const float* image;
+    const float* mask;
+    long long image_stride, mask_stride;
+    int n, h, w;
+    unsigned long long flips;
+    fg_wview oi, om;
+};
+
+constexpr int MASK_NT = 256;
+
+// one lane per aligned 4-float run of a destination row; needs w % 4 == 0, oi.sc == 1, oi.sx == 3, om.sx == 1 and
+// every base / stride a multiple of 16 bytes (wide_ok)
+__global__ void __launch_bounds__(MASK_NT) mask_tile_runs_kernel(const MaskGeo g) {
+    const long long total = (long long)g.n * g.h * g.w;
+    const int image_runs = 3 * (g.w / 4);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int q = (int)(i % g.w);
+        const long long r = i / g.w;
+        const int y = (int)(r % g.h);
+        const int ni = (int)(r / g.h);
+        const bool flip = (g.flips >> ni) & 1ull;
+        f32x4 v;
+        if (q < image_runs) {
+            const float* s = g.image + ni * g.image_stride + (long long)y * g.w * 3;
+            const int f0 = 4 * q;
+            if (!flip) {
+                v = *reinterpret_cast<const f32x4*>(s + f0);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int x = (f0 + k) / 3, c = (f0 + k) - 3 * x;
+                    v[k] = s[3 * (g.w - 1 - x) + c];
+                }
+            }
+            *reinterpret_cast<f32x4*>(g.oi.ptr + ni * g.oi.sn + y * g.oi.sy + f0) = v;
+        } else {
+            const float* s = g.mask + ni * g.mask_stride + (long long)y * g.w;
+            const int x0 = 4 * (q - image_runs);
+            if (!flip) {
+                v = *reinterpret_cast<const f32x4*>(s + x0);
+            } else {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(s + (g.w - 4 - x0));
+                v[0] = t[3]; v[1] = t[2]; v[2] = t[1]; v[3] = t[0];
+            }
+            *reinterpret_cast<f32x4*>(g.om.ptr + ni * g.om.sn + y * g.om.sy + x0) = v;
+        }
+    }
+}
+
+// one lane per pixel: any destination strides, any width, any alignment
+__global__ void __launch_bounds__(MASK_NT) mask_tile_pixels_kernel(const MaskGeo g) {
+    const long long total = (long long)g.n * g.h * g.w;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % g.w);
+        const long long r = i / g.w;
+        const int y = (int)(r % g.h);
+        const int ni = (int)(r / g.h);
+        const int xs = (g.flips >> ni) & 1ull ? g.w - 1 - x : x;
+        const long long p = (long long)y * g.w + xs;
+        const float* s = g.image + ni * g.image_stride + 3 * p;
+        float* d = g.oi.ptr + ni * g.oi.sn + y * g.oi.sy + x * g.oi.sx;
+        const float a = s[0], b = s[1], c = s[2], m = g.mask[ni * g.mask_stride + p];
+        d[0] = a;
+        d[g.oi.sc] = b;
+        d[2 * g.oi.sc] = c;
+        g.om.ptr[ni * g.om.sn + y * g.om.sy + x * g.om.sx] = m;
+    }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+bool wide_ok(const MaskGeo& g) {
+    return g.w % 4 == 0 && aligned16(g.image) && aligned16(g.mask) && g.image_stride % 4 == 0 &&
+           g.mask_stride % 4 == 0 && g.oi.sc == 1 && g.oi.sx == 3 && aligned16(g.oi.ptr) && g.oi.sn % 4 == 0 &&
+           g.oi.sy % 4 == 0 && g.om.sx == 1 && aligned16(g.om.ptr) && g.om.sn % 4 == 0 && g.om.sy % 4 == 0;
+}
+
 }  // namespace
 
 FG_API int fg_tiff_probe(const char* path, int* height, int* width, int* channels, int* sample_code) {
@@ -307,4 +402,26 @@ FG_API int fg_tile_transform(const fg_tile_batch* b, hipStream_t stream) {
     const long long v_work = (long long)B.n * B.out_h * B.out_w;
     hipLaunchKernelGGL(tile_vpass_kernel, dim3(fg::blocks_for(v_work, 256, 16384)), dim3(256), 0, stream, B, B.rows);
     return fg::launched("tile_vpass");
+}
+
+FG_API int fg_mask_tile_batch(const float* image, long long image_stride, const float* mask, long long mask_stride,
+                              int n, int h, int w, unsigned long long flips, fg_wview out_image, fg_wview out_mask,
+                              hipStream_t stream) {
+    if (!image || !mask || !out_image.ptr || !out_mask.ptr)
+        return fg::fail(FG_ERR_INVALID, "fg_mask_tile_batch: null argument");
+    if (n <= 0 || h <= 0 || w <= 0)
+        return fg::fail(FG_ERR_INVALID, "fg_mask_tile_batch: sizes must be positive (n %d, h %d, w %d)", n, h, w);
+    if (n > FG_MASK_BATCH_MAX)
+        return fg::fail(FG_ERR_INVALID, "fg_mask_tile_batch: %d tiles in one call (the flip mask holds %d)", n,
+                        (int)FG_MASK_BATCH_MAX);
+    const long long px = (long long)h * w;
+    if (image_stride < 3 * px || mask_stride < px)
+        return fg::fail(FG_ERR_INVALID, "fg_mask_tile_batch: tile strides %lld / %lld shorter than a %d x %d tile "
+                        "(%lld / %lld floats)", image_stride, mask_stride, h, w, 3 * px, px);
+    const MaskGeo g{image, mask, image_stride, mask_stride, n, h, w, flips, out_image, out_mask};
+    const dim3 grid(fg::blocks_for(n * px, MASK_NT, 4096));
+    const bool wide = wide_ok(g);
+    if (wide) hipLaunchKernelGGL(mask_tile_runs_kernel, grid, dim3(MASK_NT), 0, stream, g);
+    else hipLaunchKernelGGL(mask_tile_pixels_kernel, grid, dim3(MASK_NT), 0, stream, g);
+    return fg::launched(wide ? "mask_tile_runs" : "mask_tile_pixels");
 }

@@ -75,6 +75,7 @@ class fg_adam_tensor(C.Structure):
 
 
 FG_TILE_MAX_CH = 16
+FG_MASK_BATCH_MAX = 64
 
 FG_RENDER_SIGNED, FG_RENDER_UNIT = 0, 1
 FG_SCALAR_UNIT, FG_SCALAR_THRESHOLD, FG_SCALAR_LOGIT = 0, 1, 2
@@ -222,6 +223,8 @@ SIGNATURES = {
     "fg_tiff_probe": [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "fg_tiff_read": [C.c_char_p, C.c_void_p, C.c_longlong],
     "fg_tile_transform": [C.POINTER(fg_tile_batch), C.c_void_p],
+    "fg_mask_tile_batch": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                           C.c_ulonglong, fg_wview, fg_wview, C.c_void_p],
 }
 RESTYPES = {"fg_bernoulli_mt_workspace_words": C.c_longlong, "fg_last_error": C.c_char_p, "fg_last_launch": C.c_char_p, "fg_in_workspace_doubles": C.c_longlong, "fg_bn_workspace_doubles": C.c_longlong,
             "fg_ssim_workspace_doubles": C.c_longlong, "fg_sq_err_workspace_doubles": C.c_longlong,

@@ -14,6 +14,8 @@ device-side transform of the reference's dataset (models/data.py:11-146, models/
   determine_masks_dataset, MaskDataset, create_masks_dataset
                             models/data.py:148-218: the segmentation model's labelled tiles (host decode; plain
                             DataLoaders, as the reference)
+  MaskTileLoader            create_masks_dataset(staged=True): the same batches through TileLoader's staging
+                            machine and one HIP copy per batch (fg_mask_tile_batch: np.fliplr, HWC -> CHW)
 
 There is no CPU transform path: the loader needs a HIP device, like the rest of floodgan.
 """
@@ -378,17 +380,18 @@ class _Slot:
         self.consumed.record()
 
 
-class TileLoader:
-    """The reference's DataLoader (models/data.py:28-42: batch_size, shuffle=True, pin_memory=True) as an
-    MI355X pipeline: a producer thread decodes each batch's tiles (libfloodgan, GIL released, `workers`
-    threads) into a pinned-host ring slot and issues its H2D on a dedicated copy stream; the consumer's
-    stream waits for that copy and runs the transform, so decode + PCIe of batch i+1 overlap the
-    training step on batch i.  Yields (input [B,C,R,R], target [B,3,R,R], names), channels-last.
+class _StagedLoader:
+    """The staging machine TileLoader and MaskTileLoader share: the index order of a real DataLoader, a producer
+    thread that decodes each batch's tile pairs (libfloodgan, GIL released, `workers` threads) straight into a
+    pinned-host ring slot and issues its H2D on a dedicated copy stream, and a consumer whose stream waits for that
+    copy, turns the device slot into fresh output tensors (`_output`) and hands the slot back.  The `h2d` /
+    `consumed` events guard the two halves of a slot, so decode + PCIe of batch i+1 overlap the step on batch i.
+    Leaving the iteration early (break, an exception in the loop body, a dropped generator) stops the producer;
+    a producer-side exception is re-raised by the consumer.
 
-    Order: that of torch.utils.data.DataLoader(shuffle=True) over the item indices (the same draws from
-    the global torch RNG when the iteration starts as the reference's loader).  Data parallelism: each global batch of
-    batch_size * world items is split in rank order (every rank gets batch_size items; the last, short
-    global batch is dropped when world > 1 so the shards stay equal)."""
+    A subclass gives `_geometry(item)` -> (h, w, cx, cy) of one item's tile pair (raising for a pair it cannot
+    stage), `_match(item)` (raising when a later item does not fit the ring, which is sized from the first) and
+    `_output(slot, items)` -> the batch to yield; items are the dataset's `item(index)` tuples, paths first."""
 
     def __init__(self, dataset, batch_size=1, shuffle=True, device="cuda", prefetch=2, workers=4, rank=0, world=1,
                  drop_last=False):
@@ -421,39 +424,16 @@ class TileLoader:
     def _ensure(self, first_index):
         if self._slots is not None:
             return
-        inp, outp, _, _, _ = self.ds.item(first_index)
-        h, w, cx, _ = tiff_probe(inp)
-        hy, wy, cy, _ = tiff_probe(outp)
-        if (hy, wy) != (h, w):
-            raise RuntimeError(f"input {h}x{w} and target {hy}x{wy} tiles differ in size")
-        self.geom = (h, w, cx, cy)
+        h, w, cx, cy = self.geom = self._geometry(self.ds.item(first_index))
         self._slots = [_Slot(self.bs, h, w, cx, cy, self.device) for _ in range(self.prefetch + 1)]
         self._copy = torch.cuda.Stream(device=self.device)
 
     def _decode(self, pool, slot, items):
-        h, w, cx, cy = self.geom
-
         def one(k):
-            inp, outp, _, _, _ = items[k]
-            if tiff_probe(inp)[:3] != (h, w, cx) or tiff_probe(outp)[:3] != (h, w, cy):
-                raise RuntimeError(f"tile {inp} does not match the batch geometry {h}x{w}")
-            read_tile(inp, slot.hx[k].numpy())
-            read_tile(outp, slot.hy[k].numpy())
+            self._match(items[k])
+            read_tile(items[k][0], slot.hx[k].numpy())
+            read_tile(items[k][1], slot.hy[k].numpy())
         list(pool.map(one, range(len(items))))
-
-    def _transform(self, dx, dy, flips, crops):
-        n = dx.shape[0]
-        h, w = dx.shape[1], dx.shape[2]
-        rh, rw = resized_size(h, w, self.ds.resize)
-        _, _, oh, ow = crop_window(rh, rw, self.ds.crop, 0)
-        f = torch.tensor([int(v) for v in flips], dtype=torch.int32).to(self.device, non_blocking=True)
-        xo = torch.empty((n, len(self.ds.chan), oh, ow), dtype=torch.float32, device=self.device,
-                         memory_format=torch.channels_last)
-        yo = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
-        _, k1 = transform_batch(dx, f, crops, self.ds.chan, self.ds.resize, self.ds.crop, xo)
-        _, k2 = transform_batch(dy, f, crops, [0, 1, 2], self.ds.resize, self.ds.crop, yo)
-        self._keep = [f, k1, k2]
-        return xo, yo
 
     def __iter__(self):
         batches = list(self._batches())
@@ -499,11 +479,10 @@ class TileLoader:
                 slot, items = got
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(slot.h2d)
-                n = len(items)
-                xo, yo = self._transform(slot.dx[:n], slot.dy[:n], [it[2] for it in items], [it[3] for it in items])
+                out = self._output(slot, items)
                 slot.consumed.record(cur)
                 free.put(slot)
-                yield xo, yo, [it[4] for it in items]
+                yield out
         finally:
             stop.set()
             while th.is_alive():
@@ -513,6 +492,50 @@ class TileLoader:
                 except (queue.Empty, queue.Full):
                     pass
             th.join()
+
+
+class TileLoader(_StagedLoader):
+    """The reference's DataLoader (models/data.py:28-42: batch_size, shuffle=True, pin_memory=True) as an
+    MI355X pipeline: a producer thread decodes each batch's tiles (libfloodgan, GIL released, `workers`
+    threads) into a pinned-host ring slot and issues its H2D on a dedicated copy stream; the consumer's
+    stream waits for that copy and runs the transform, so decode + PCIe of batch i+1 overlap the
+    training step on batch i.  Yields (input [B,C,R,R], target [B,3,R,R], names), channels-last.
+
+    Order: that of torch.utils.data.DataLoader(shuffle=True) over the item indices (the same draws from
+    the global torch RNG when the iteration starts as the reference's loader).  Data parallelism: each global batch of
+    batch_size * world items is split in rank order (every rank gets batch_size items; the last, short
+    global batch is dropped when world > 1 so the shards stay equal)."""
+
+    def _geometry(self, item):
+        h, w, cx, _ = tiff_probe(item[0])
+        hy, wy, cy, _ = tiff_probe(item[1])
+        if (hy, wy) != (h, w):
+            raise RuntimeError(f"input {h}x{w} and target {hy}x{wy} tiles differ in size")
+        return h, w, cx, cy
+
+    def _match(self, item):
+        h, w, cx, cy = self.geom
+        if tiff_probe(item[0])[:3] != (h, w, cx) or tiff_probe(item[1])[:3] != (h, w, cy):
+            raise RuntimeError(f"tile {item[0]} does not match the batch geometry {h}x{w}")
+
+    def _transform(self, dx, dy, flips, crops):
+        n = dx.shape[0]
+        h, w = dx.shape[1], dx.shape[2]
+        rh, rw = resized_size(h, w, self.ds.resize)
+        _, _, oh, ow = crop_window(rh, rw, self.ds.crop, 0)
+        f = torch.tensor([int(v) for v in flips], dtype=torch.int32).to(self.device, non_blocking=True)
+        xo = torch.empty((n, len(self.ds.chan), oh, ow), dtype=torch.float32, device=self.device,
+                         memory_format=torch.channels_last)
+        yo = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
+        _, k1 = transform_batch(dx, f, crops, self.ds.chan, self.ds.resize, self.ds.crop, xo)
+        _, k2 = transform_batch(dy, f, crops, [0, 1, 2], self.ds.resize, self.ds.crop, yo)
+        self._keep = [f, k1, k2]
+        return xo, yo
+
+    def _output(self, slot, items):
+        n = len(items)
+        xo, yo = self._transform(slot.dx[:n], slot.dy[:n], [it[2] for it in items], [it[3] for it in items])
+        return xo, yo, [it[4] for it in items]
 
 
 def create_flood_dataset(dataset_subset, dataset_dem, path, topography, resize=None, crop=None, batch_size=1,
@@ -554,6 +577,12 @@ class MaskDataset(torch.utils.data.Dataset):
     def __init__(self, data, path):
         self.data_files, self.path = data, path
 
+    def item(self, index):
+        """(image path, mask path, flipped, name) of item `index` (what the staged loader batches)"""
+        image_path, version = self.data_files[index][0], self.data_files[index][1]
+        return (f"{self.path}/masks_input/{image_path}", f"{self.path}/masks_output/{image_path}",
+                version == "flipped", image_path)
+
     def __getitem__(self, index):
         image_path, version = self.data_files[index][0], self.data_files[index][1]
         image = read_tile(f"{self.path}/masks_input/{image_path}")
@@ -570,13 +599,87 @@ class MaskDataset(torch.utils.data.Dataset):
         return len(self.data_files)
 
 
+def mask_batch(raw_image, raw_mask, flips, out_image, out_mask):
+    """fg_mask_tile_batch over raw segmentation tiles already on the device: np.fliplr of the flipped tiles and the
+    HWC -> CHW transpose, a bit-exact copy.  raw_image [n, h, w, 3] and raw_mask [n, h, w] (or [n, h, w, 1]) fp32,
+    each tile contiguous; flips: one truth value per tile (host); out_image [n, 3, h, w] and out_mask [n, 1, h, w],
+    any strides.  The flip choice travels by value, FG_MASK_BATCH_MAX tiles per call: larger batches are split."""
+    L.require_device(raw_image, "raw image tiles")
+    L.require_device(raw_mask, "raw mask tiles")
+    L.require_device(out_image, "image batch")
+    L.require_device(out_mask, "mask batch")
+    n, h, w, c = raw_image.shape
+    if raw_mask.dim() == 4 and raw_mask.shape[3] == 1:
+        raw_mask = raw_mask[..., 0]
+    flips = [bool(f) for f in flips]
+    if (c != 3 or tuple(raw_mask.shape) != (n, h, w) or tuple(out_image.shape) != (n, 3, h, w)
+            or tuple(out_mask.shape) != (n, 1, h, w) or len(flips) != n):
+        raise ValueError(f"mask_batch: raw tiles {tuple(raw_image.shape)} / {tuple(raw_mask.shape)}, outputs "
+                         f"{tuple(out_image.shape)} / {tuple(out_mask.shape)}, {len(flips)} flips do not agree")
+    if not (raw_image[0].is_contiguous() and raw_mask[0].is_contiguous()):
+        raise ValueError("mask_batch: each raw tile must be contiguous")
+    lib, stream = L.load(), L.stream_handle(raw_image.device)
+    for i in range(0, n, L.FG_MASK_BATCH_MAX):
+        xi, mi, oi, om = (t[i:i + L.FG_MASK_BATCH_MAX] for t in (raw_image, raw_mask, out_image, out_mask))
+        bits = sum(1 << k for k, f in enumerate(flips[i:i + L.FG_MASK_BATCH_MAX]) if f)
+        L.check(lib.fg_mask_tile_batch(xi.data_ptr(), xi.stride(0) if xi.shape[0] > 1 else h * w * 3, mi.data_ptr(),
+                                       mi.stride(0) if mi.shape[0] > 1 else h * w, xi.shape[0], h, w, bits,
+                                       L.fg_wview(oi.data_ptr(), *oi.stride()), L.fg_wview(om.data_ptr(), *om.stride()),
+                                       stream), "mask_tile_batch")
+    return out_image, out_mask
+
+
+class MaskTileLoader(_StagedLoader):
+    """create_masks_dataset's DataLoader (models/data.py:148-177) as the staged pipeline of TileLoader: the same
+    ring, producer and events, read_tile straight into the pinned slot with no host flip and no host transpose,
+    and one fg_mask_tile_batch per batch.  Yields what DataLoader(MaskDataset, shuffle=True) yields -- (image
+    [B, 3, H, W], mask [B, 1, H, W], [names]), the items in the same order under the same global RNG state, the
+    last short batch kept -- but on the device, the image channels-last, in fresh tensors (the slot is free again
+    once the kernel has passed).  All tiles of one loader share one geometry (the ring is sized from the first);
+    the image must have 3 channels, the mask 1."""
+
+    def __init__(self, dataset, batch_size=1, shuffle=True, device="cuda", prefetch=2, workers=4):
+        super().__init__(dataset, batch_size, shuffle, device, prefetch, workers)
+
+    dataset = property(lambda self: self.ds)
+    batch_size = property(lambda self: self.bs)
+
+    def _geometry(self, item):
+        h, w, c, _ = tiff_probe(item[0])
+        hm, wm, cm, _ = tiff_probe(item[1])
+        if c != 3 or cm != 1:
+            raise ValueError(f"MaskTileLoader: {item[3]}: the image tile must have 3 channels and the mask tile 1 "
+                             f"(got {c} and {cm})")
+        if (hm, wm) != (h, w):
+            raise RuntimeError(f"MaskTileLoader: {item[3]}: image {h}x{w} and mask {hm}x{wm} tiles differ in size")
+        return h, w, c, cm
+
+    def _match(self, item):
+        h, w = self._geometry(item)[:2]
+        if (h, w) != self.geom[:2]:
+            raise RuntimeError(f"MaskTileLoader: {item[3]}: a {h}x{w} tile in a loader staged for "
+                               f"{self.geom[0]}x{self.geom[1]} tiles (all tiles of one loader share one size)")
+
+    def _output(self, slot, items):
+        n = len(items)
+        h, w = self.geom[:2]
+        image = torch.empty((n, 3, h, w), dtype=torch.float32, device=self.device, memory_format=torch.channels_last)
+        mask = torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device)
+        mask_batch(slot.dx[:n], slot.dy[:n], [it[2] for it in items], image, mask)
+        return image, mask, [it[3] for it in items]
+
+
 def create_masks_dataset(dataset_subset, path, train_on_all, batch_size=1, num_workers=0,
-                         csv_path="metadata/masks_metadata.csv"):
+                         csv_path="metadata/masks_metadata.csv", staged=False, device="cuda", prefetch=2):
     """models/data.py:148-177: (train, validation, test) DataLoaders (shuffled, pinned) over MaskDataset; only the
-    training loader when train_on_all"""
+    training loader when train_on_all.  staged=True: MaskTileLoaders over the same datasets (the same batches, in
+    the same order, already on `device`)"""
     train_data, val_data, test_data = determine_masks_dataset(dataset_subset, train_on_all, csv_path)
 
     def loader(data):
+        if staged:
+            return MaskTileLoader(MaskDataset(data, path), batch_size=batch_size, shuffle=True, device=device,
+                                  prefetch=prefetch, workers=num_workers if num_workers else 4)
         return DataLoader(dataset=MaskDataset(data, path), batch_size=batch_size, num_workers=num_workers,
                           shuffle=True, pin_memory=torch.cuda.is_available())
 

@@ -473,7 +473,9 @@ class SegmentationModel:
     LambdaLR of lambda_rule, starting_epoch resumed from the checkpoint; train_model() runs the fused SegStep.
     The loaders come from floodgan.data.create_masks_dataset when data_path is given, or are assigned
     (train_loader / val_loader / test_loader: iterables of (image, mask, names)).  Every keyword of the reference's
-    constructor is accepted (segment.py passes them all).  Pictures go through floodgan.render: save_images_interval
+    constructor is accepted (segment.py passes them all); staged_loader=True (not a keyword of the reference's) asks
+    create_masks_dataset for MaskTileLoaders, whose batches are the same and arrive on the device.  Pictures go
+    through floodgan.render: save_images_interval
     writes the sample sheet (plot_sample_images(num_images=10)) every that many epochs, plot_mask_image(path) the
     predicted mask of one image; the constructor's plot_mask_image= is kept in mask_image_path for the caller
     (segment.py calls the method itself); both need a data_path to write under and raise without one.  The
@@ -482,7 +484,7 @@ class SegmentationModel:
     def __init__(self, data_path=None, pretrained_model_path=None, train=False, device="cuda", seed=47,
                  dataset_subset="usa", num_epochs=100, train_on_all=False, save_model_interval=0, verbose=True,
                  save_images_interval=0, plot_mask_image=None, use_test_data=False,
-                 csv_path="metadata/masks_metadata.csv"):
+                 csv_path="metadata/masks_metadata.csv", staged_loader=False):
         if (save_images_interval != 0 or plot_mask_image) and data_path is None:
             # the pictures are written under {data_path}/images (models/segmentation_model.py:102, :205)
             raise NotImplementedError("floodgan: the segmentation model's pictures (save_images_interval != 0: "
@@ -494,7 +496,7 @@ class SegmentationModel:
         self.data_path, self.pretrained_model_path, self.seed = data_path, pretrained_model_path, seed
         self.dataset_subset, self.train_on_all, self.train = dataset_subset, train_on_all, train
         self.save_model_interval, self.verbose, self.csv_path = save_model_interval, verbose, csv_path
-        self.device = device
+        self.device, self.staged_loader = device, staged_loader
         self.starting_epoch = 1
         self.current_epoch, self.num_epochs, self.all_losses, self.all_accuracies = 1, num_epochs, [], []
         self.model = UNet().apply(initialise_weights).to(device)
@@ -517,7 +519,8 @@ class SegmentationModel:
 
     def _loaders(self):
         from .data import create_masks_dataset
-        return create_masks_dataset(self.dataset_subset, self.data_path, self.train_on_all, csv_path=self.csv_path)
+        return create_masks_dataset(self.dataset_subset, self.data_path, self.train_on_all, csv_path=self.csv_path,
+                                    staged=self.staged_loader, device=self.device)
 
     def lambda_rule(self, epoch):
         """models/segmentation_model.py:86-92: constant for the first half of the epochs, then linear decay"""

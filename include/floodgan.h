@@ -713,6 +713,21 @@ typedef struct fg_tile_batch {
 } fg_tile_batch;
 int fg_tile_transform(const fg_tile_batch* batch, hipStream_t stream);
 
+enum { FG_MASK_BATCH_MAX = 64 };
+/* A batch of staged raw segmentation tiles -> the MaskDataset item layout (models/data.py:187-198): np.fliplr of the
+ * "flipped" version and the HWC -> CHW transpose, nothing else (mask tiles are not normalised), so every output
+ * float is a copy of one input float.
+ *   image: device, n raw tiles [h, w, 3] fp32, image_stride floats apart; mask: device, n raw tiles [h, w] fp32,
+ *   mask_stride floats apart; flips: bit i set = mirror the columns of tile i (by value: nothing on the device to
+ *   keep alive, n <= FG_MASK_BATCH_MAX);
+ *   out_image[i, c, y, x] = image[i, y, flip_i ? w - 1 - x : x, c], a strided [n, 3, h, w] view;
+ *   out_mask[i, 0, y, x]  = mask[i, y, flip_i ? w - 1 - x : x], a strided [n, 1, h, w] view (sc unused).
+ * Fails (FG_ERR_INVALID, nothing written) on a null pointer, a size that is not positive, n > FG_MASK_BATCH_MAX or a
+ * tile stride shorter than a tile. */
+int fg_mask_tile_batch(const float* image, long long image_stride, const float* mask, long long mask_stride, int n,
+                       int h, int w, unsigned long long flips, fg_wview out_image, fg_wview out_mask,
+                       hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
