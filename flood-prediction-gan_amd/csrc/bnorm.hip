@@ -364,6 +364,32 @@ __global__ void bn_bwd_apply_kernel(const BwdIn I, const float* __restrict__ coe
     if (am) absmax_flush(m, am);
 }
 
+// The backward through FIXED per-channel statistics (module.eval(): mean / invstd do not depend on x, so the adjoint
+// has no mean terms): dst = gy * gamma * invstd, one streaming pass that reads src and the gradient(s) once and
+// writes dst once (16-byte accesses; src is read for the activation gates only)
+__global__ void bn_bwd_fixed_apply_kernel(const BwdIn I, fg_view dst, unsigned* am) {
+    const int C = I.src.c_alloc, C4 = C / 4;
+    const long long total = (long long)I.src.n * I.src.h * I.src.w * C4;
+    unsigned m = 0;
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(idx % C4);
+        long long pix = idx / C4;
+        const int x = (int)(pix % I.src.w);
+        pix /= I.src.w;
+        const int y = (int)(pix % I.src.h);
+        const int n = (int)(pix / I.src.h);
+        f32x4 gy, xh;
+        grad_and_xhat(I, n, y, x, c4, gy, xh);
+        f32x4 o = gy;
+        if (I.gamma) o = o * ld4(I.gamma + 4 * c4);
+        o = o * ld4(I.invstd + 4 * c4);
+        *reinterpret_cast<f32x4*>(dst.ptr + fg::vidx(dst, n, y, x) + 4 * c4) = o;
+        m = max(m, absbits4(o));
+    }
+    if (am) absmax_flush(m, am);
+}
+
 // 2x2 / stride-2 max pool (nn.MaxPool2d(2), models/model_architectures.py:558-560): floor sizes
 __global__ void maxpool2_kernel(fg_view src, fg_view dst) {
     const int C = src.c_alloc, C4 = C / 4;
@@ -491,6 +517,40 @@ FG_API int fg_bn_bwd(fg_view gA, int actA, fg_view gB, int actB, fg_view src, in
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(fg::blocks_for(total, NT, 4096)), dim3(NT), 0, stream, I, coef, dst,
                        reinterpret_cast<unsigned*>(absmax));
     return fg::launched("bn_bwd_apply");
+}
+
+FG_API int fg_bn_bwd_fixed(fg_view gA, int actA, fg_view gB, int actB, fg_view src, const float* mean,
+                           const float* invstd, const float* gamma, const float* beta, fg_view dst, float* gamma_grad,
+                           float* beta_grad, int accumulate, double* work, float* absmax, hipStream_t stream) {
+    const bool sums = gamma_grad || beta_grad;
+    if (!ok_view(gA) || !aligned(gA) || !ok_view(src) || !aligned(src) || !ok_view(dst) || !aligned(dst) || !mean ||
+        !invstd || NT % (src.c_alloc / 4) != 0 || ((!gamma) != (!beta)) || (sums && !work))
+        return fg::fail(FG_ERR_INVALID, "fg_bn_bwd_fixed: bad args (C=%d)", src.c_alloc);
+    for (const fg_view* v : {&gA, &gB, &dst}) {
+        if (!v->ptr) continue;
+        if (!aligned(*v) || v->n != src.n || v->h != src.h || v->w != src.w || v->c_alloc < src.c_alloc)
+            return fg::fail(FG_ERR_INVALID, "fg_bn_bwd_fixed: view %dx%dx%d (c %d) vs source %dx%dx%d (c %d)", v->n,
+                            v->h, v->w, v->c_alloc, src.n, src.h, src.w, src.c_alloc);
+    }
+    BwdIn I{gA, gB, src, actA, actB, src.n, mean, invstd, gamma, beta, make_drop(nullptr, 1.f, 0ull)};
+    const int C = src.c_alloc;
+    if (sums) {
+        // sum gy and sum gy * xhat over the whole batch (one group); the finalize kernel's apply coefficients are
+        // written beside the partials and not read
+        const int chunks = choose_chunks(1, (long long)src.h * src.w);
+        float* coef = reinterpret_cast<float*>(work + (size_t)MAX_PARTIALS * C * 2);
+        hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(chunks, 1), dim3(NT), 0, stream, I, chunks, work);
+        int e = fg::launched("bn_bwd_stats");
+        if (e) return e;
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, stream, src.n, C, 1,
+                           src.h * src.w, chunks, work, coef, gamma_grad, beta_grad, accumulate);
+        e = fg::launched("bn_bwd_finalize");
+        if (e) return e;
+    }
+    const long long total = (long long)src.n * src.h * src.w * (C / 4);
+    hipLaunchKernelGGL(bn_bwd_fixed_apply_kernel, dim3(fg::blocks_for(total, NT, 4096)), dim3(NT), 0, stream, I, dst,
+                       reinterpret_cast<unsigned*>(absmax));
+    return fg::launched("bn_bwd_fixed_apply");
 }
 
 FG_API int fg_dropout_mask(unsigned long long seed, float keep, long long total, float* dst, hipStream_t stream) {

@@ -38,6 +38,27 @@ __global__ void unit_image_kernel(fg_sview src, int n, int c, int h, int w, floa
     }
 }
 
+// backward of unit_image_kernel: dst[n, c, y, x] (+)= scale * 0.5 * g[n, y, x, c] where the forward did not clamp
+__global__ void unit_image_bwd_kernel(fg_view g, fg_sview src, int n, int c, int h, int w, float scale, fg_wview dst,
+                                      int accumulate) {
+    const long long total = (long long)n * c * h * w;
+    const float k = scale * 0.5f;                     // exact
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % w);
+        long long r = i / w;
+        const int y = (int)(r % h);
+        r /= h;
+        const int ch = (int)(r % c);
+        const int ni = (int)(r / c);
+        const float v = __fmul_rn(__fadd_rn(src.ptr[ni * src.sn + ch * src.sc + y * src.sy + x * src.sx], 1.f), 0.5f);
+        // ATen's clamp backward: both ends inclusive, nothing for NaN
+        const float gv = v >= 0.f && v <= 1.f ? g.ptr[fg::vidx(g, ni, y, x) + ch] : 0.f;
+        float* d = dst.ptr + ni * dst.sn + ch * dst.sc + y * dst.sy + x * dst.sx;
+        *d = accumulate ? __fmaf_rn(k, gv, *d) : __fmul_rn(k, gv);
+    }
+}
+
 __device__ __forceinline__ void block_sum2(double& a, double& b) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -206,6 +227,18 @@ FG_API int fg_unit_image(fg_sview src, int n, int c, int h, int w, float* dst, f
     hipLaunchKernelGGL(unit_image_kernel, dim3(fg::blocks_for(total, NT, 4096)), dim3(NT), 0, stream, src, n, c, h, w,
                        dst, buf);
     return fg::launched("unit_image");
+}
+
+FG_API int fg_unit_image_bwd(fg_view g, fg_sview src, int n, int c, int h, int w, float scale, fg_wview dst,
+                             int accumulate, hipStream_t stream) {
+    if (!g.ptr || !src.ptr || !dst.ptr || n <= 0 || c <= 0 || h <= 0 || w <= 0 || g.n != n || g.h != h || g.w != w ||
+        g.c_alloc < c || g.pad < 0)
+        return fg::fail(FG_ERR_INVALID, "fg_unit_image_bwd: bad args (gradient %dx%dx%d c %d for an image %dx%dx%dx%d)",
+                        g.n, g.h, g.w, g.c_alloc, n, c, h, w);
+    const long long total = (long long)n * c * h * w;
+    hipLaunchKernelGGL(unit_image_bwd_kernel, dim3(fg::blocks_for(total, NT, 4096)), dim3(NT), 0, stream, g, src, n, c,
+                       h, w, scale, dst, accumulate);
+    return fg::launched("unit_image_bwd");
 }
 
 FG_API long long fg_ssim_workspace_doubles(int n, int c, int h, int w) {

@@ -6,6 +6,9 @@
 //     channel and the border written as zero), and train_model's accuracy count
 //     #{(sigmoid(z) > 0.5) == (t > 0.5)} -- one pass over the gradient view's padded extent.  sigmoid(z) > 0.5
 //     is decided as z > 0 (the fp32 sigmoid of a positive z is > 0.5 down to z ~ 6e-8, of z <= 0 never).
+//   * fg_flood_mask_bce: the same pass with the target taken from a second logits view, t = flood(r) ? 1 : 0 (the
+//     flood-mask loss of floodgan.segmentation.FloodMaskLoss); its count is the number of agreeing mask pixels,
+//     tp + tn of fg_mask_confusion on the same two views.
 //   * fg_maxpool2_bwd: the gradient of fg_maxpool2, routed to the FIRST maximum of each 2x2 window in the scan
 //     order (0,0), (0,1), (1,0), (1,1) (ATen's rule: a later element wins only when strictly greater, or NaN),
 //     recomputed from the saved source; all four positions are written, so no pre-zeroing and no dependence on
@@ -23,9 +26,28 @@ constexpr int BCE_BLOCKS_MAX = 1024;
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
 
+// The two targets of the BCE pass: a contiguous [N, 1, H, W] tensor (fg_bce_logits; an element counts as correct when
+// (z > 0) == (t > 0.5)), or the flood mask of a second logits view (fg_flood_mask_bce: t = fg::flood(r), the decision
+// fg_mask_confusion and the renderer make; correct when fg::flood(z) makes the same one)
+struct DenseTarget {
+    const float* __restrict__ p;
+    __device__ __forceinline__ float operator()(int n, int y, int x, int h, int w) const {
+        return p[((size_t)n * h + y) * w + x];
+    }
+    __device__ __forceinline__ bool agrees(float v, float t) const { return (v > 0.f) == (t > 0.5f); }
+};
+struct MaskTarget {
+    fg_view r;
+    __device__ __forceinline__ float operator()(int n, int y, int x, int, int) const {
+        return fg::flood(r.ptr[fg::vidx(r, n, y, x)]) ? 1.f : 0.f;
+    }
+    __device__ __forceinline__ bool agrees(float v, float t) const { return fg::flood(v) == (t != 0.f); }
+};
+
 // thread = one pixel of g's padded extent (all of its channel quads); partial[blk] = (loss sum, correct count)
-__global__ void __launch_bounds__(NT) bce_logits_kernel(fg_view z, const float* __restrict__ target, float gscale,
-                                                        fg_view g, double* __restrict__ partial) {
+template <class Target>
+__global__ void __launch_bounds__(NT) bce_logits_kernel(fg_view z, const Target target, float gscale, fg_view g,
+                                                        double* __restrict__ partial) {
     const int hp = g.h + 2 * g.pad, wp = g.w + 2 * g.pad, C4 = g.c_alloc / 4;
     const long long total = (long long)g.n * hp * wp;
     float loss = 0.f;
@@ -38,14 +60,14 @@ __global__ void __launch_bounds__(NT) bce_logits_kernel(fg_view z, const float* 
         f32x4 o = {0.f, 0.f, 0.f, 0.f};
         if (xx >= 0 && xx < g.w && yy >= 0 && yy < g.h) {
             const float v = z.ptr[fg::vidx(z, n, yy, xx)];
-            const float t = target[((size_t)n * g.h + yy) * g.w + xx];
+            const float t = target(n, yy, xx, g.h, g.w);
             const float e = expf(-fabsf(v));                      // in (0, 1]
             loss += fmaxf(v, 0.f) - v * t + log1pf(e);
             // sigmoid(v) and 1 - sigmoid(v), each without cancellation: s - t = s (1 - t) - (1 - s) t
             const float big = 1.f / (1.f + e), small = e / (1.f + e);
             const float s = v >= 0.f ? big : small, s1 = v >= 0.f ? small : big;
             o[0] = (s * (1.f - t) - s1 * t) * gscale;
-            correct += (v > 0.f) == (t > 0.5f);
+            correct += target.agrees(v, t);
         }
         float* dst = g.ptr + (size_t)idx * g.c_alloc;
         st4(dst, o);
@@ -163,11 +185,34 @@ FG_API int fg_bce_logits(fg_view logits, const float* target, float gscale, fg_v
                         logits.h, logits.w, grad.n, grad.h, grad.w, grad.c_alloc);
     const long long total = (long long)grad.n * (grad.h + 2 * grad.pad) * (grad.w + 2 * grad.pad);
     const int blocks = fg::blocks_for(total, NT, BCE_BLOCKS_MAX);
-    hipLaunchKernelGGL(bce_logits_kernel, dim3(blocks), dim3(NT), 0, stream, logits, target, gscale, grad, work);
+    hipLaunchKernelGGL(bce_logits_kernel<DenseTarget>, dim3(blocks), dim3(NT), 0, stream, logits, DenseTarget{target},
+                       gscale, grad, work);
     int e = fg::launched("bce_logits");
     if (e) return e;
     hipLaunchKernelGGL(bce_finalize_kernel, dim3(1), dim3(NT), 0, stream, work, blocks,
                        (double)logits.n * logits.h * logits.w, loss, correct);
+    return fg::launched("bce_finalize");
+}
+
+FG_API int fg_flood_mask_bce(fg_view logits, fg_view ref_logits, float gscale, fg_view grad, void* result, double* work,
+                             hipStream_t stream) {
+    if (!ok_view(logits) || !ok_view(grad) || !ref_logits.ptr || ref_logits.c_alloc <= 0 || ref_logits.pad < 0 ||
+        !result || ((uintptr_t)result & 7) || !work || grad.n != logits.n || grad.h != logits.h ||
+        grad.w != logits.w || ref_logits.n != logits.n || ref_logits.h != logits.h || ref_logits.w != logits.w)
+        return fg::fail(FG_ERR_INVALID,
+                        "fg_flood_mask_bce: bad args (logits %dx%dx%d, reference %dx%dx%d, gradient %dx%dx%d c %d)",
+                        logits.n, logits.h, logits.w, ref_logits.n, ref_logits.h, ref_logits.w, grad.n, grad.h, grad.w,
+                        grad.c_alloc);
+    const long long total = (long long)grad.n * (grad.h + 2 * grad.pad) * (grad.w + 2 * grad.pad);
+    const int blocks = fg::blocks_for(total, NT, BCE_BLOCKS_MAX);
+    hipLaunchKernelGGL(bce_logits_kernel<MaskTarget>, dim3(blocks), dim3(NT), 0, stream, logits,
+                       MaskTarget{ref_logits}, gscale, grad, work);
+    int e = fg::launched("flood_mask_bce");
+    if (e) return e;
+    // result: 16 bytes, the fp32 loss in the low half (its upper word is not written), the int64 count in the high
+    hipLaunchKernelGGL(bce_finalize_kernel, dim3(1), dim3(NT), 0, stream, work, blocks,
+                       (double)logits.n * logits.h * logits.w, reinterpret_cast<float*>(result),
+                       reinterpret_cast<long long*>(result) + 1);
     return fg::launched("bce_finalize");
 }
 

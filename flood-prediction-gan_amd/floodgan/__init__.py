@@ -14,7 +14,7 @@ from .model_architectures import (AttentionGANBlock, AttentionGANDiscriminator, 
                                   AttentionGANGenerator, CycleGANBlock, CycleGANDiscriminator, CycleGANGenerator,
                                   PairedAttentionBlock, PairedAttentionDiscriminator, PairedAttentionGenerator,
                                   Pix2PixBlock, Pix2PixDiscriminator, Pix2PixGenerator)
-from .segmentation import UNet  # noqa: F401
+from .segmentation import FloodMaskLoss, UNet  # noqa: F401
 from .evaluate import LPIPS, compare_output_images, load_lpips_weights  # noqa: F401
 from .png import read_png, write_png  # noqa: F401
 from .render import Canvas, colormap_lut, save_image, save_sheet, sheet_layout  # noqa: F401
@@ -22,6 +22,6 @@ from .render import Canvas, colormap_lut, save_image, save_sheet, sheet_layout  
 __all__ = ["PairedAttentionGenerator", "PairedAttentionBlock", "PairedAttentionDiscriminator",
            "AttentionGANGenerator", "AttentionGANBlock", "AttentionGANDiscriminator",
            "CycleGANGenerator", "CycleGANBlock", "CycleGANDiscriminator",
-           "Pix2PixGenerator", "Pix2PixBlock", "Pix2PixDiscriminator", "UNet", "load_library", "LPIPS",
+           "Pix2PixGenerator", "Pix2PixBlock", "Pix2PixDiscriminator", "UNet", "FloodMaskLoss", "load_library", "LPIPS",
            "load_lpips_weights", "Canvas", "colormap_lut", "save_image", "save_sheet", "sheet_layout", "write_png",
            "read_png", "compare_output_images"]

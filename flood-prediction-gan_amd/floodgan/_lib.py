@@ -195,11 +195,15 @@ SIGNATURES = {
     "fg_bn_bwd": [fg_view, C.c_int, fg_view, C.c_int, fg_view, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_float, C.c_ulonglong, fg_view, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                   C.c_void_p, C.c_void_p],
+    "fg_bn_bwd_fixed": [fg_view, C.c_int, fg_view, C.c_int, fg_view, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                        fg_view, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "fg_dropout_mask": [C.c_ulonglong, C.c_float, C.c_longlong, C.c_void_p, C.c_void_p],
     "fg_bernoulli_mt_workspace_words": [C.c_int],
     "fg_bernoulli_mt": [C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong, C.c_int,
                         C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
     "fg_unit_image": [fg_sview, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, fg_view, C.c_void_p],
+    "fg_unit_image_bwd": [fg_view, fg_sview, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, fg_wview, C.c_int,
+                          C.c_void_p],
     "fg_ssim_workspace_doubles": [C.c_int, C.c_int, C.c_int, C.c_int],
     "fg_ssim": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float,
                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -216,6 +220,7 @@ SIGNATURES = {
     "fg_maxpool2_bwd": [fg_view, fg_view, fg_view, C.c_void_p, C.c_void_p],
     "fg_bce_logits_workspace_doubles": [],
     "fg_bce_logits": [fg_view, C.c_void_p, C.c_float, fg_view, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fg_flood_mask_bce": [fg_view, fg_view, C.c_float, fg_view, C.c_void_p, C.c_void_p, C.c_void_p],
     "fg_render_rgb": [fg_sview, C.c_int, C.c_int, C.c_int, C.c_int, fg_canvas, C.c_int, C.c_int, C.c_int, C.c_int,
                       C.c_void_p],
     "fg_render_scalar": [fg_sview, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, fg_canvas, C.c_int, C.c_int,

@@ -31,7 +31,14 @@ TOPOGRAPHY_CHANNELS = {"all": 9, "map": 6, "dem": 4, "flow": 4, "river": 4, None
 
 class PairedStep:
     """One paired-GAN training iteration on device tensors x [N,C,H,W], y [N,3,H,W].
-    Returns a device tensor [D real, D synthetic, G synthetic, 100*L1] (models/model.py:648-651)."""
+    Returns a device tensor [D real, D synthetic, G synthetic, 100*L1] (models/model.py:648-651).
+
+    fake_loss (None by default): an extra generator term, an object with a `weight` and a call
+    fake_loss(fake, y, g_fake, scale) made between the L1 term and the G step's discriminator backward; it adds
+    scale * dL/d(fake) into g_fake (scale = weight / world size) and returns weight * L as a one-element device
+    tensor, which becomes a fifth entry of the returned losses (FloodMaskLoss.fused_term is one)."""
+
+    fake_loss = None
 
     def __init__(self, generator, discriminator, opt_g, opt_d, group=None):
         self.G, self.D = generator, discriminator
@@ -93,6 +100,8 @@ class PairedStep:
         ops.mse_const(pred, 1.0, inv, losses[2:3], g_pred)
         g_fake = torch.empty(N, 3, x.shape[2], x.shape[3], dtype=torch.float32, device=dev)
         ops.l1(fake, y, 100.0 * inv, losses[3:4], g_fake, loss_scale=100.0)     # logged as 100 * L1 (:643-651)
+        if self.fake_loss is not None:
+            losses = torch.cat([losses, self.fake_loss(fake, y, g_fake, self.fake_loss.weight * inv)])
         X.disc_backward(self.dp, dS, g_pred, param_grads=False, input_grad=g_fake, input_grad_channels=(C, 3),
                         input_grad_accumulate=True)
         if rec is not None:
@@ -182,6 +191,8 @@ class Pix2PixStep(PairedStep):
         ops.mse_const(pred, 1.0, inv, losses[2:3], g_pred)
         g_fake = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
         ops.l1(fake, y, 100.0 * inv, losses[3:4], g_fake, loss_scale=100.0)     # logged as 100 * L1 (:643-651)
+        if self.fake_loss is not None:
+            losses = torch.cat([losses, self.fake_loss(fake, y, g_fake, self.fake_loss.weight * inv)])
         P2P.disc_backward(self.dp, dS, g_pred, param_grads=False, input_grad=g_fake, input_grad_channels=(C, 3),
                           input_grad_accumulate=True)
         if rec is not None:
@@ -209,7 +220,17 @@ class Model:
                  save_images_interval=0, verbose=False, load_pretrained_model=False, pretrained_model_path=None,
                  add_identity_loss=False, training_model=True, seed=47, device="cuda", train_loader=None,
                  val_loader=None, test_loader=None, batch_size=1, num_workers=0,
-                 csv_path="metadata/dataset_split.csv"):
+                 csv_path="metadata/dataset_split.csv", flood_mask_weight=0.0, segmentation_model_path=None,
+                 flood_mask_batch_stats=False):
+        # flood_mask_weight > 0 (not a keyword of the reference's): the paired step's generator also descends
+        # weight * FloodMaskLoss(fake, target) of the segmentation U-Net at segmentation_model_path
+        self.flood_mask_weight = float(flood_mask_weight)
+        self.segmentation_model_path, self.flood_mask_batch_stats = segmentation_model_path, flood_mask_batch_stats
+        if self.flood_mask_weight < 0:
+            raise ValueError(f"flood_mask_weight must be >= 0 (got {flood_mask_weight})")
+        if self.flood_mask_weight > 0 and not segmentation_model_path:
+            raise ValueError("flood_mask_weight > 0 needs segmentation_model_path: the checkpoint of the trained "
+                             "segmentation U-Net the flood-mask loss is measured with")
         saved = None
         if load_pretrained_model:
             # models/model.py:52-57: the checkpoint, not the `model` argument, names the architecture
@@ -230,6 +251,8 @@ class Model:
         self.training_model, self.seed, self.device = training_model, seed, device
         self.model_is_cycle = self.model in ("attentiongan", "cyclegan")
         self.model_is_attention = self.model in ("pairedattention", "attentiongan")     # models/model.py:219-229
+        if self.flood_mask_weight > 0 and self.model_is_cycle:
+            raise NotImplementedError("the flood-mask loss is a term of the paired step (PairedAttention, Pix2Pix)")
 
         input_channels = TOPOGRAPHY_CHANNELS[self.topography]
         torch.manual_seed(self.seed)
@@ -325,14 +348,25 @@ class Model:
         if self.model_is_cycle:
             keys = LOSS_KEYS + (IDENTITY_KEYS if self.add_identity_loss else [])
             return {pre + k: [] for k in keys}
-        return {f"{pre}losses_discriminator_real": [], f"{pre}losses_discriminator_synthetic": [],
-                f"{pre}losses_generator_synthetic": [], f"{pre}l1_losses_generator_synthetic": []}
+        return {pre + k: [] for k in self.paired_loss_keys()}
+
+    def paired_loss_keys(self):
+        """the reference's four keys, in the order the fused step returns its losses; the flood-mask term's when on"""
+        keys = ["losses_discriminator_real", "losses_discriminator_synthetic", "losses_generator_synthetic",
+                "l1_losses_generator_synthetic"]
+        return keys + (["losses_flood_mask_generator_synthetic"] if self.flood_mask_weight > 0 else [])
 
     @property
     def step_fn(self):
         if self._step is None:
             cls = Pix2PixStep if self.model == "pix2pix" else PairedStep
             self._step = cls(self.generator, self.discriminator, self.optimizer_generator, self.optimizer_discriminator)
+            if self.flood_mask_weight > 0:
+                from .segmentation import FloodMaskLoss
+                with torch.random.fork_rng(devices=[]):      # (the U-Net is initialised before its checkpoint loads)
+                    loss = FloodMaskLoss(self.segmentation_model_path, batch_stats=self.flood_mask_batch_stats)
+                self.flood_mask_loss = loss.to(self.device)
+                self._step.fake_loss = loss.fused_term(self.flood_mask_weight)
         return self._step
 
     def train_paired(self):
@@ -340,8 +374,7 @@ class Model:
         if self.train_loader is None:
             raise RuntimeError("no training data: pass data_path (floodgan.data loaders, as models/model.py:150-156) "
                                "or train_loader (an iterable of (input, target, names))")
-        keys = ["losses_discriminator_real", "losses_discriminator_synthetic", "losses_generator_synthetic",
-                "l1_losses_generator_synthetic"]
+        keys = self.paired_loss_keys()
         for epoch in range(self.starting_epoch, self.num_epochs + 1):
             t0 = time.time()
             losses = self.initialise_loss_storage(overall=False)

@@ -878,6 +878,19 @@ def bn_bwd(gA, actA, gB, actB, src, groups, mean, invstd, gamma, beta, drop, dst
                              L.ptr(_bn_work(src.n, src.c, src.t.device)), L.ptr(slot), L.stream_handle()), "bn_bwd")
 
 
+def bn_bwd_fixed(gA, actA, gB, actB, src, mean, invstd, gamma, beta, dst, gamma_grad=None, beta_grad=None,
+                 accumulate=False):
+    """bn_bwd through fixed per-channel statistics (eval mode: bn_eval_stats): dst = gy * gamma * invstd.  Without
+    parameter gradients it is one streaming launch and takes no workspace"""
+    L.require_device(_tensor(src), "BatchNorm source")
+    slot = _dst_slot(dst, None)
+    sums = gamma_grad is not None or beta_grad is not None
+    work = _bn_work(src.n, src.c, src.t.device) if sums else None
+    L.check(_lib().fg_bn_bwd_fixed(view(gA), actA, view(gB), actB, view(src), L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
+                                   L.ptr(beta), view(dst), L.ptr(gamma_grad), L.ptr(beta_grad), int(accumulate),
+                                   L.ptr(work), L.ptr(slot), L.stream_handle()), "bn_bwd_fixed")
+
+
 def dropout_mask(seed, shape, device):
     """the 0/1 keep decisions bn_apply makes for `seed` over a tensor of NCHW `shape` (float32, device)"""
     out = torch.empty(shape, dtype=torch.float32, device=device)
@@ -919,6 +932,33 @@ def bce_logits(logits, target, gscale, grad, loss_out, correct_out=None):
     wrote(grad)
     L.check(_lib().fg_bce_logits(view(logits), L.ptr(target), C.c_float(gscale), view(grad), L.ptr(loss_out),
                                  L.ptr(correct_out), L.ptr(work), L.stream_handle()), "bce_logits")
+
+
+def flood_mask_bce(logits, ref_logits, gscale, grad, result):
+    """bce_logits against the flood mask of ref_logits (channel 0 of a view of the same grid; t = flood(r), the
+    decision of fg_mask_confusion).  result: int64[2] on the device -- the fp32 loss in the low half of [0], the
+    count of pixels whose own flood decision equals t in [1] (SegStep.read unpacks it)"""
+    L.require_device(_tensor(logits), "logits")
+    assert isinstance(grad, Buf)
+    if result.dtype != torch.int64 or result.numel() != 2 or not result.is_contiguous() or not result.is_cuda:
+        raise RuntimeError("flood_mask_bce: the result must be a contiguous int64[2] tensor on the device")
+    work = torch.empty(int(_lib().fg_bce_logits_workspace_doubles()), dtype=torch.float64, device=result.device)
+    wrote(grad)
+    L.check(_lib().fg_flood_mask_bce(view(logits), view(ref_logits), C.c_float(gscale), view(grad), L.ptr(result),
+                                     L.ptr(work), L.stream_handle()), "flood_mask_bce")
+
+
+def unit_image_bwd(g, x, dst, scale=1.0, accumulate=False):
+    """the backward of segmentation.unit_image: dst [N, C, H, W] (fp32, any strides) (+)= scale * 0.5 * g * gate, g
+    the U-Net input gradient (Buf, c >= C), x the image the forward read, gate = 0 <= (x + 1) * 0.5 <= 1 in fp32"""
+    L.require_device(x, "image")
+    L.require_device(dst, "image gradient")
+    N, Cc, H, W = x.shape
+    if tuple(dst.shape) != (N, Cc, H, W):
+        raise RuntimeError(f"unit_image_bwd: gradient {tuple(dst.shape)} for an image {tuple(x.shape)}")
+    wrote(dst)
+    L.check(_lib().fg_unit_image_bwd(view(g), sview(x), N, Cc, H, W, C.c_float(scale), sview(dst), int(accumulate),
+                                     L.stream_handle()), "unit_image_bwd")
 
 
 # ------------------------------------------------------------------ LPIPS (evaluate.LPIPS)

@@ -60,24 +60,35 @@ def check_input_size(H, W):
                            "does not implement")
 
 
-def _double_conv(P, B, names, X, mid, out, training, dsts, save=None):
+def _stats(B, name, src, training, update_running):
+    """P2P._stats, or -- a frozen network evaluated as the reference evaluates it -- the batch statistics with the
+    running statistics and num_batches_tracked left alone"""
+    if training and not update_running:
+        return ops.bn_stats(src, 1, None)
+    return P2P._stats(B, name, src, 1, training)
+
+
+def _double_conv(P, B, names, X, mid, out, training, dsts, save=None, operands=True, update_running=True):
     """DoubleConv over X (zero border 1): returns nothing; dsts = (dst0, dst1) of the second ReLU.  save (dict):
-    receives what _double_conv_bwd reads"""
+    receives what _double_conv_bwd reads -- without operands, only what the gates and the input gradients read (the
+    conv outputs and their statistics), not the conv inputs the weight gradients read"""
     c1, b1, c2, b2 = names
     N, h, w = X.n, X.h, X.w
     dev = X.t.device
     t = Buf.empty(N, h, w, mid, 0, dev)
     P2P._conv_nb(P, c1, X, 1, 3, 1, t)
-    mean, invstd = P2P._stats(B, b1, t, 1, training)
+    mean, invstd = _stats(B, b1, t, training, update_running)
     a = Buf.zeros(N, h, w, mid, 1, dev)
     ops.bn_apply(t, 1, mean, invstd, P[b1 + ".weight"], P[b1 + ".bias"], None, FG_ACT_RELU, a)
     u = Buf.empty(N, h, w, out, 0, dev)
     P2P._conv_nb(P, c2, a, 1, 3, 1, u)
-    mean2, invstd2 = P2P._stats(B, b2, u, 1, training)
+    mean2, invstd2 = _stats(B, b2, u, training, update_running)
     ops.bn_apply(u, 1, mean2, invstd2, P[b2 + ".weight"], P[b2 + ".bias"], None, FG_ACT_RELU, dsts[0],
                  FG_ACT_RELU if dsts[1] is not None else 0, dsts[1])
     if save is not None:
-        save.update(x=X, t=t, m1=mean, i1=invstd, a=a, u=u, m2=mean2, i2=invstd2)
+        save.update(t=t, m1=mean, i1=invstd, u=u, m2=mean2, i2=invstd2)
+        if operands:
+            save.update(x=X, a=a)
 
 
 def _convT2(P, name, X, Y):
@@ -88,16 +99,21 @@ def _convT2(P, name, X, Y):
     ops.conv(PL.phase_problems(X, w.shape, 2, 0, Y, wps, maps, bias=P.get(name + ".bias")))
 
 
-def unet_logits(P, B, X0, training=True, save=False):
+def unet_logits(P, B, X0, training=True, save=False, update_running=True):
     """Forward of UNet(3, 1) over X0 (Buf: the [0, 1] image in channels 0..2 of 4, zero border 1).
     Returns the logits Buf [N, H, W, 4] (channel 0); with save=True, (logits, S): S holds the activations
-    unet_backward reads (nothing is kept otherwise)."""
+    unet_backward reads (nothing is kept otherwise).  save="input": the state of unet_backward(param_grads=False)
+    only -- the pre-BatchNorm conv outputs with their statistics and the max-pool sources, not the conv and
+    ConvTranspose inputs that only weight gradients read.  update_running=False (with training): batch statistics
+    that leave running_mean, running_var and num_batches_tracked untouched (a frozen network evaluated as the
+    reference evaluates it)."""
     N, H, W = X0.n, X0.h, X0.w
     check_input_size(H, W)
     dev = X0.t.device
     enc, dec, head = layer_names()
-    S = dict(N=N, H=H, W=W, training=training, enc=[{} for _ in range(5)], dec=[{} for _ in range(4)]) if save \
-        else None
+    full = save != "input"                                           # (with save) the weight gradients' operands too
+    S = dict(N=N, H=H, W=W, training=training, operands=full, enc=[{} for _ in range(5)],
+             dec=[{} for _ in range(4)]) if save else None
     cats = [Buf.zeros(N, H >> k, W >> k, 2 * ENC[k], 1, dev) for k in range(4)]     # decoder inputs by level
     X = X0
     for k in range(5):
@@ -105,14 +121,15 @@ def unet_logits(P, B, X0, training=True, save=False):
         if k < 4:
             x = Buf.empty(N, h, w, ENC[k], 0, dev)                 # max-pool source
             _double_conv(P, B, enc[k], X, ENC[k], ENC[k], training, (x, Slice(cats[k], 0, ENC[k])),
-                         S["enc"][k] if save else None)
+                         S["enc"][k] if save else None, full, update_running)
             X = Buf.zeros(N, h // 2, w // 2, ENC[k], 1, dev)
             ops.maxpool2(x, X)
         else:
             x = Buf.zeros(N, h, w, ENC[k], 1, dev)
-            _double_conv(P, B, enc[k], X, ENC[k], ENC[k], training, (x, None), S["enc"][k] if save else None)
+            _double_conv(P, B, enc[k], X, ENC[k], ENC[k], training, (x, None), S["enc"][k] if save else None, full,
+                         update_running)
             X = x
-        if save:
+        if save and (full or k < 4):
             S["enc"][k]["out"] = x                                 # the level output (k < 4: the max-pool source)
     for i, (up, names) in enumerate(dec):                            # up1 .. up4
         k = 3 - i                                                    # the encoder level it joins
@@ -120,8 +137,9 @@ def unet_logits(P, B, X0, training=True, save=False):
         _convT2(P, up, X, Slice(cats[k], c, c))
         last = i == len(dec) - 1
         y = Buf.zeros(N, H >> k, W >> k, c, 0 if last else 1, dev)
-        _double_conv(P, B, names, cats[k], c, c, training, (y, None), S["dec"][i] if save else None)
-        if save:
+        _double_conv(P, B, names, cats[k], c, c, training, (y, None), S["dec"][i] if save else None, full,
+                     update_running)
+        if save and full:
             S["dec"][i].update(xin=X, out=y)                       # the ConvTranspose input, the level output
         X = y
     logits = Buf.empty(N, H, W, 4, 0, dev)
@@ -129,35 +147,51 @@ def unet_logits(P, B, X0, training=True, save=False):
     return (logits, S) if save else logits
 
 
-def _double_conv_bwd(P, G, names, D, gA, gB=None, need_input=True, split=None):
+def _bn_bwd(G, P, name, gA, gB, src, mean, invstd, dst, fixed, param_grads):
+    """BatchNorm + ReLU backward of one DoubleConv half: through the batch statistics, or (fixed: an eval-mode
+    forward) through the fixed ones; without param_grads the gamma / beta sums are not formed"""
+    gg, gb = (G.get(name + ".weight"), G.get(name + ".bias")) if param_grads else (None, None)
+    actB = FG_ACT_RELU if gB is not None else 0
+    if fixed:
+        ops.bn_bwd_fixed(gA, FG_ACT_RELU, gB, actB, src, mean, invstd, P[name + ".weight"], P[name + ".bias"], dst,
+                         gg, gb, G.acc)
+    else:
+        ops.bn_bwd(gA, FG_ACT_RELU, gB, actB, src, 1, mean, invstd, P[name + ".weight"], P[name + ".bias"], None, dst,
+                   gg, gb, G.acc)
+
+
+def _double_conv_bwd(P, G, names, D, gA, gB=None, need_input=True, split=None, fixed=False, param_grads=True):
     """Backward of _double_conv from its saved tensors D.  The gradient of the DoubleConv's output is
     gA * relu' (+ gB * relu': an encoder level's two consumers).  Returns the input gradient (None when not
     needed: inc's image), as one Buf or, with split=c, as the two Bufs of its channels [0, c) and [c, 2c) (a decoder
-    level's cat: the skip half and the ConvTranspose half), both written by one launch."""
+    level's cat: the skip half and the ConvTranspose half), both written by one launch.  fixed: the forward ran on
+    fixed (eval-mode) statistics.  param_grads=False: input gradients only (D then needs no conv inputs)."""
     c1, b1, c2, b2 = names
-    u, t, a, x = D["u"], D["t"], D["a"], D["x"]
+    u, t = D["u"], D["t"]
     N, h, w = u.n, u.h, u.w
     dev = u.t.device
     g_u = Buf.empty(N, h, w, u.c, 1, dev)                  # zero border 1: the full correlation of a 3x3, pad 1
-    ops.bn_bwd(gA, FG_ACT_RELU, gB, FG_ACT_RELU if gB is not None else 0, u, 1, D["m2"], D["i2"], P[b2 + ".weight"],
-               P[b2 + ".bias"], None, g_u, G.get(b2 + ".weight"), G.get(b2 + ".bias"), G.acc)
+    _bn_bwd(G, P, b2, gA, gB, u, D["m2"], D["i2"], g_u, fixed, param_grads)
     ops.zero_border(g_u)
-    X._wgrad_conv(P, G, c2, g_u, a, 1, 3, 1)
-    g_a = Buf.empty(N, h, w, a.c, 0, dev)
+    if param_grads:
+        X._wgrad_conv(P, G, c2, g_u, D["a"], 1, 3, 1)
+    g_a = Buf.empty(N, h, w, t.c, 0, dev)
     X._dgrad_s1(P, c2, g_u, 1, 3, g_a)
     g_t = Buf.empty(N, h, w, t.c, 1, dev)
-    ops.bn_bwd(g_a, FG_ACT_RELU, None, 0, t, 1, D["m1"], D["i1"], P[b1 + ".weight"], P[b1 + ".bias"], None, g_t,
-               G.get(b1 + ".weight"), G.get(b1 + ".bias"), G.acc)
+    _bn_bwd(G, P, b1, g_a, None, t, D["m1"], D["i1"], g_t, fixed, param_grads)
     ops.zero_border(g_t)
-    X._wgrad_conv(P, G, c1, g_t, x, 1, 3, 1)
+    if param_grads:
+        X._wgrad_conv(P, G, c1, g_t, D["x"], 1, 3, 1)
     if not need_input:
         return None
     wt = P[c1 + ".weight"]
+    c_in = wt.shape[1]
     if split is None:
-        g_x = Buf.empty(N, h, w, x.c, 0, dev)
+        # (inc: 3 image channels in a 4-channel buffer, the engine writing 3 -- as the head writes 1 of 4)
+        g_x = Buf.empty(N, h, w, c_in, 0, dev) if c_in % 4 == 0 else Buf.zeros(N, h, w, PL.rup(c_in, 4), 0, dev)
         X._dgrad_s1(P, c1, g_t, 1, 3, g_x)
         return g_x
-    assert x.c == 2 * split
+    assert c_in == 2 * split
     halves, probs = [], []
     for c0 in (0, split):
         g_h = Buf.empty(N, h, w, split, 0, dev)
@@ -168,14 +202,16 @@ def _double_conv_bwd(P, G, names, D, gA, gB=None, need_input=True, split=None):
     return halves
 
 
-def _convT2_bwd(P, G, name, xin, g_y):
+def _convT2_bwd(P, G, name, xin, g_y, param_grads=True):
     """Backward of _convT2 (ConvTranspose2d(k=2, s=2, p=0), weight (I, O, 2, 2)): g_y [N, 2h, 2w, O] (no border
-    needed: the four taps tile the output) -> the gradient of xin [N, h, w, I]; weight and bias gradients into G"""
+    needed: the four taps tile the output) -> the gradient of xin [N, h, w, I]; weight and bias gradients into G
+    (param_grads=False: neither, and xin is not read)"""
     wt = P[name + ".weight"]
-    G.wgrad(PL.wgrad_convT(xin, g_y, 2, 0, wt.shape[0]), PL.wmap_wgrad(wt.shape, True, g_y.c, 2), name + ".weight",
-            (xin, g_y))
-    ops.channel_sum(g_y, wt.shape[1], G.get(name + ".bias"), G.acc)
-    g_x = Buf.empty(xin.n, xin.h, xin.w, wt.shape[0], 0, g_y.t.device)
+    if param_grads:
+        G.wgrad(PL.wgrad_convT(xin, g_y, 2, 0, wt.shape[0]), PL.wmap_wgrad(wt.shape, True, g_y.c, 2),
+                name + ".weight", (xin, g_y))
+        ops.channel_sum(g_y, wt.shape[1], G.get(name + ".bias"), G.acc)
+    g_x = Buf.empty(g_y.n, g_y.h // 2, g_y.w // 2, wt.shape[0], 0, g_y.t.device)
     m = PL.wmap_convT_dgrad(wt.shape, g_y.c)
     ops.conv([PL.conv_problem(g_y, 0, 2, 2, ops.pack_weight(wt, m), m, g_x)])     # one GEMM, K = 4 O
     return g_x
@@ -186,13 +222,19 @@ EVAL_BACKWARD = ("floodgan: the segmentation UNet's backward runs through the ba
                  "is not implemented")
 
 
-def unet_backward(P, S, g_logits, grads_into=None, choices=None):
-    """Explicit backward of unet_logits(save=True) through training-mode BatchNorm.  g_logits: Buf [N, H, W, >= 4],
-    dL/d(logits) in channel 0.  Returns {parameter name: gradient} (written into grads_into[name] when given).  The
-    gradient of the input image is not computed.  choices (dict, test instrumentation): receives
-    {"pool<k>": uint8 NCHW} -- the window position each max-pool gradient went to."""
-    if not S["training"]:
-        raise RuntimeError(EVAL_BACKWARD)
+def unet_backward(P, S, g_logits, grads_into=None, choices=None, *, input_grad=False, param_grads=True):
+    """Explicit backward of unet_logits(save=True).  g_logits: Buf [N, H, W, >= 4], dL/d(logits) in channel 0.
+    Returns {parameter name: gradient} (written into grads_into[name] when given).  A forward in training mode goes
+    back through its batch statistics, one in eval mode (S["training"] False) through the fixed statistics it used
+    (fg_bn_bwd_fixed).  input_grad=True: also the gradient of the input image -- inc's first conv's input gradient on
+    the conv engine, a Buf [N, H, W, 4] (channels 0..2) under the key "input".  param_grads=False: no weight, bias or
+    BatchNorm parameter gradient is formed (a frozen network inside a loss); S may then come from
+    unet_logits(save="input").  choices (dict, test instrumentation): receives {"pool<k>": uint8 NCHW} -- the window
+    position each max-pool gradient went to."""
+    if param_grads and not S["operands"]:
+        raise RuntimeError("unet_backward: parameter gradients need the conv inputs, which a forward saved with "
+                           "save=\"input\" does not keep (use save=True, or param_grads=False)")
+    fixed = not S["training"]
     N, H, W = S["N"], S["H"], S["W"]
     if (g_logits.n, g_logits.h, g_logits.w) != (N, H, W):
         raise RuntimeError(f"unet_backward: logits gradient {g_logits.n}x{g_logits.h}x{g_logits.w} for a saved "
@@ -201,8 +243,9 @@ def unet_backward(P, S, g_logits, grads_into=None, choices=None):
     G = X._Grads(P, grads_into, device=dev)
     enc, dec, head = layer_names()
     # ---- OutConv 1x1, 64 -> 1 (weight + bias, then the input gradient)
-    y = S["dec"][3]["out"]
-    ops.conv1x1_wgrad(g_logits, y, 1, G.get(head + ".weight"), G.get(head + ".bias"), G.acc)
+    if param_grads:
+        y = S["dec"][3]["out"]
+        ops.conv1x1_wgrad(g_logits, y, 1, G.get(head + ".weight"), G.get(head + ".bias"), G.acc)
     g = Buf.empty(N, H, W, 64, 0, dev)
     ops.conv1x1_dgrad(g_logits, P[head + ".weight"], 1, g)
     # ---- decoder, up4 .. up1
@@ -211,8 +254,8 @@ def unet_backward(P, S, g_logits, grads_into=None, choices=None):
         k = 3 - i
         up, names = dec[i]
         D = S["dec"][i]
-        g_skip[k], g_up = _double_conv_bwd(P, G, names, D, g, split=ENC[k])
-        g = _convT2_bwd(P, G, up, D["xin"], g_up)
+        g_skip[k], g_up = _double_conv_bwd(P, G, names, D, g, split=ENC[k], fixed=fixed, param_grads=param_grads)
+        g = _convT2_bwd(P, G, up, D.get("xin"), g_up, param_grads)
     # ---- encoder, down4 .. inc
     for k in range(4, -1, -1):
         E = S["enc"][k]
@@ -227,8 +270,11 @@ def unet_backward(P, S, g_logits, grads_into=None, choices=None):
                 choices[f"pool{k}"] = ch.permute(0, 3, 1, 2)
             ops.maxpool2_bwd(src, g, gA, ch)
             gB = g_skip.pop(k)
-        g = _double_conv_bwd(P, G, enc[k], E, gA, gB, need_input=k > 0)
+        g = _double_conv_bwd(P, G, enc[k], E, gA, gB, need_input=k > 0 or input_grad, fixed=fixed,
+                             param_grads=param_grads)
     G.join()
+    if input_grad:
+        G.out["input"] = g
     return G.out
 
 
@@ -269,7 +315,8 @@ class _UNetFn(torch.autograd.Function):
     """forward: the native executor; activations are saved only when a gradient can be computed from them: the
     caller's grad mode on (autograd runs forward with grad mode off, so it arrives as `save`), a parameter needing
     one, and the module in train() mode.  backward: unet_backward on the parameters autograd saved (an in-place
-    update of one between forward and backward is caught by its version check)"""
+    update of one between forward and backward is caught by its version check).  With module.input_grad set, the
+    input image may need a gradient too (alone: the save="input" state), and eval() mode saves as train() does"""
 
     @staticmethod
     def forward(ctx, module, save, x, *params):
@@ -278,13 +325,14 @@ class _UNetFn(torch.autograd.Function):
         B = dict(module.named_buffers())
         _, X0 = unit_image_passthrough(x)
         wants_x, wants_p = bool(save and ctx.needs_input_grad[2]), bool(save and any(ctx.needs_input_grad[3:]))
-        if wants_x:
+        full = module.input_grad                         # the switch: input gradient, and a backward in eval mode
+        if wants_x and not full:
             raise RuntimeError("floodgan: the segmentation UNet does not compute the gradient of its input image "
-                               "(pass an input with requires_grad=False)")
-        ctx.S, ctx.eval_mode = None, wants_p and not module.training
-        if wants_p and module.training:
-            logits, ctx.S = unet_logits(P, B, X0, True, save=True)
-            ctx.keys = keys
+                               "(pass an input with requires_grad=False, or set UNet.input_grad = True)")
+        ctx.S, ctx.eval_mode = None, wants_p and not module.training and not full
+        if (wants_p and module.training) or (full and (wants_x or wants_p)):
+            logits, ctx.S = unet_logits(P, B, X0, module.training, save=True if wants_p else "input")
+            ctx.keys, ctx.wants = keys, (wants_x, wants_p)
             ctx.save_for_backward(*params)
         else:
             logits = unet_logits(P, B, X0, module.training)
@@ -298,10 +346,13 @@ class _UNetFn(torch.autograd.Function):
             raise RuntimeError("floodgan: segmentation UNet backward without a saved forward")
         P, S = dict(zip(ctx.keys, ctx.saved_tensors)), ctx.S
         ctx.S = None                                     # (a second backward through the same graph is an error)
+        wants_x, wants_p = ctx.wants
         g_logits = Buf.empty(S["N"], S["H"], S["W"], 4, 0, g.device)
         ops.pack_input(g, 1, None, 0, g_logits, 0, S["N"], FG_PAD_ZERO)
-        grads = unet_backward(P, S, g_logits)
-        return (None, None, None) + tuple(grads[k] if need else None for k, need in zip(P, ctx.needs_input_grad[3:]))
+        grads = unet_backward(P, S, g_logits, input_grad=wants_x, param_grads=wants_p)
+        g_x = grads["input"].interior()[..., :3].permute(0, 3, 1, 2).contiguous() if wants_x else None
+        return (None, None, g_x) + tuple(grads[k] if need and wants_p else None
+                                         for k, need in zip(P, ctx.needs_input_grad[3:]))
 
 
 def unit_image_passthrough(x):
@@ -373,7 +424,11 @@ class OutConv(nn.Module):
 class UNet(nn.Module):
     """models/model_architectures.py:508-538 -- same modules, registration order and state_dict keys;
     forward = the native executor (logits [N, 1, H, W]); in train() mode it trains under stock loss.backward() and
-    any torch optimizer (no gradient of the input image; no backward in eval() mode)."""
+    any torch optimizer (no gradient of the input image; no backward in eval() mode).  Setting input_grad = True
+    lifts both limits: an input that requires a gradient gets one, and a backward in eval() mode runs through the
+    fixed running statistics (parameter gradients included)."""
+
+    input_grad = False
 
     def __init__(self, n_channels=3, n_classes=1, bilinear=False):
         super().__init__()
@@ -463,6 +518,134 @@ class SegStep:
         """(loss, accuracy) on the host from a step's result: one device-to-host copy"""
         host = res.cpu()
         return float(host[:1].view(torch.float32)[0]), int(host[1]) / numel
+
+
+# ------------------------------------------------------------------------------------------ the flood-mask loss
+
+def _flood_mask_pass(P, B, fake, real, batch_stats, save):
+    """The forward half of the flood-mask loss on two [N, 3, H, W] images in [-1, 1]: fg_unit_image on both, the
+    frozen U-Net on both (the `real` pass keeps nothing; the `fake` pass keeps the save="input" state when `save`),
+    fg_flood_mask_bce of the fake logits against the mask of the real ones.  Returns (result, g, S, logits, ref):
+    result = the 16-byte (loss, agreeing pixels) tensor SegStep.read unpacks, g = dL/d(logits) for the mean loss."""
+    N, _, H, W = fake.shape
+    _, F0 = unit_image(fake, buf=True, nchw=False)
+    _, R0 = unit_image(real, buf=True, nchw=False)
+    ref = unet_logits(P, B, R0, batch_stats, update_running=False)
+    out = unet_logits(P, B, F0, batch_stats, save="input" if save else False, update_running=False)
+    logits, S = out if save else (out, None)
+    res = torch.empty(2, dtype=torch.int64, device=fake.device)
+    g = Buf.empty(N, H, W, 4, 0, fake.device)
+    ops.flood_mask_bce(logits, ref, 1.0 / (N * H * W), g, res)
+    return res, g, S, logits, ref
+
+
+class _FloodMaskFn(torch.autograd.Function):
+    """FloodMaskLoss as one autograd node: differentiable in `fake` only; the U-Net's parameters are constants"""
+
+    @staticmethod
+    def forward(ctx, owner, save, fake, real):
+        P, B = owner._state()
+        wants = bool(save and ctx.needs_input_grad[2])
+        res, g, S, _, _ = _flood_mask_pass(P, B, fake, real, owner.batch_stats, wants)
+        owner._last = (res, g.n * g.h * g.w)
+        ctx.state = (P, S, g) if wants else None
+        if wants:
+            ctx.save_for_backward(fake)
+        return res[:1].view(torch.float32)[0].clone()
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        if ctx.state is None:
+            raise RuntimeError("floodgan: FloodMaskLoss backward without a saved forward")
+        (fake,) = ctx.saved_tensors
+        (P, S, g), ctx.state = ctx.state, None           # (a second backward through the same graph is an error)
+        g_in = unet_backward(P, S, g, input_grad=True, param_grads=False)["input"]
+        g_fake = torch.empty_like(fake)
+        ops.unit_image_bwd(g_in, fake, g_fake)
+        return None, None, g_fake.mul_(g_loss), None
+
+
+class _FusedFloodMaskTerm:
+    """FloodMaskLoss as PairedStep.fake_loss: called as term(fake, real, g_fake, scale) between the L1 term and the
+    G step's discriminator backward, it adds scale * dL/d(fake) into g_fake and returns weight * L as a device
+    tensor of one element (no host synchronisation)"""
+
+    def __init__(self, loss, weight):
+        self.loss, self.weight = loss, float(weight)
+
+    def __call__(self, fake, real, g_fake, scale):
+        loss = self.loss
+        loss._check_images(fake, real)
+        P, B = loss._state()
+        res, g, S, _, _ = _flood_mask_pass(P, B, fake, real, loss.batch_stats, True)
+        loss._last = (res, g.n * g.h * g.w)
+        g_in = unet_backward(P, S, g, input_grad=True, param_grads=False)["input"]
+        ops.unit_image_bwd(g_in, fake, g_fake, scale=scale, accumulate=True)
+        return res[:1].view(torch.float32)[:1] * self.weight
+
+
+class FloodMaskLoss(nn.Module):
+    """The score the evaluation gives a generator, as a loss: binary cross-entropy of the segmentation U-Net's flood
+    logits of `fake` against the flood mask the same U-Net sees in `real` (floodgan.evaluate: MaskConfusion counts
+    the agreement of exactly these two masks).  seg_model: a drop-in UNet, a SegmentationModel or a checkpoint path;
+    its parameters and buffers are never written.  batch_stats=False: BatchNorm on the running statistics (eval
+    mode); True: on the statistics of each batch, as the reference evaluates the model -- the running statistics
+    and num_batches_tracked stay untouched in both.  forward(fake, real): two [N, 3, H, W] device images in
+    [-1, 1] -> a scalar, differentiable with respect to `fake` only; nothing is saved when `fake` needs no
+    gradient or under torch.no_grad()."""
+
+    def __init__(self, seg_model, batch_stats=False):
+        super().__init__()
+        import os
+        if isinstance(seg_model, (str, os.PathLike)):
+            from .evaluate import segmentation_model
+            seg_model = segmentation_model(os.fspath(seg_model))
+        elif isinstance(seg_model, SegmentationModel):
+            seg_model = seg_model.model
+        if not isinstance(seg_model, UNet):
+            raise TypeError("FloodMaskLoss takes a floodgan UNet, a SegmentationModel or a checkpoint path "
+                            f"(got {type(seg_model).__name__})")
+        seg_model._check()
+        self.seg, self.batch_stats = seg_model, bool(batch_stats)
+        self._last = None
+
+    def _state(self):
+        return dict(self.seg.named_parameters()), dict(self.seg.named_buffers())
+
+    @staticmethod
+    def _check_images(fake, real):
+        require_device(fake, "flood-mask loss image")
+        require_device(real, "flood-mask loss target")
+        if fake.dim() != 4 or fake.shape[1] != 3 or fake.shape != real.shape:
+            raise RuntimeError(f"FloodMaskLoss takes two [N, 3, H, W] images (got {tuple(fake.shape)} and "
+                               f"{tuple(real.shape)})")
+
+    def forward(self, fake, real):
+        self._check_images(fake, real)
+        return _FloodMaskFn.apply(self, torch.is_grad_enabled(), fake, real.detach())
+
+    def read(self):
+        """(loss, fraction of agreeing mask pixels) of the last call: one device-to-host copy"""
+        if self._last is None:
+            raise RuntimeError("FloodMaskLoss.read before any call")
+        return SegStep.read(*self._last)
+
+    @property
+    def agreement(self):
+        """the last call's fraction of pixels whose two flood masks agree (MaskConfusion's Accuracy of the batch)"""
+        return self.read()[1]
+
+    def logits(self, fake, real):
+        """the two logits tensors [N, 1, H, W] the loss is formed from (nothing is saved)"""
+        self._check_images(fake, real)
+        with torch.no_grad():
+            P, B = self._state()
+            _, _, _, z, r = _flood_mask_pass(P, B, fake, real, self.batch_stats, False)
+        return tuple(b.interior()[..., :1].permute(0, 3, 1, 2).contiguous() for b in (z, r))
+
+    def fused_term(self, weight):
+        """this loss as the fake_loss hook of the fused paired step (PairedStep / Pix2PixStep)"""
+        return _FusedFloodMaskTerm(self, weight)
 
 
 class SegmentationModel:

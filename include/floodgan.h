@@ -560,6 +560,15 @@ int fg_bn_bwd(fg_view gA, int actA, fg_view gB, int actB, fg_view src, int group
               const float* invstd, const float* gamma, const float* beta, const float* drop_mask,
               float drop_scale, unsigned long long drop_seed, fg_view dst, float* gamma_grad, float* beta_grad,
               int accumulate, double* work, float* absmax, hipStream_t stream);
+/* fg_bn_bwd through FIXED per-channel statistics (module.eval(): mean = running_mean, invstd = 1 / sqrt(running_var
+ * + eps), as fg_bn_eval_stats gives them; [C] each, no groups, no dropout): with gy formed as in fg_bn_bwd,
+ * dst = gy * gamma * invstd -- the statistics do not depend on x, so there are no mean terms.  gamma_grad and
+ * beta_grad both NULL: one launch, a streaming pass that uses no workspace (work may be NULL).  Otherwise
+ * beta_grad = sum gy and gamma_grad = sum gy * xhat (written, or added to when accumulate) come from fg_bn_bwd's
+ * partial-sum and finalize kernels first; work >= fg_bn_workspace_doubles(n, c). */
+int fg_bn_bwd_fixed(fg_view gA, int actA, fg_view gB, int actB, fg_view src, const float* mean, const float* invstd,
+                    const float* gamma, const float* beta, fg_view dst, float* gamma_grad, float* beta_grad,
+                    int accumulate, double* work, float* absmax, hipStream_t stream);
 /* The 0/1 keep decisions of fg_bn_apply's hashed dropout for elements 0 .. total-1 (NCHW order of the
  * tensor the dropout applies to) into dst as floats (tests / host inspection). */
 int fg_dropout_mask(unsigned long long seed, float keep, long long total, float* dst, hipStream_t stream);
@@ -594,6 +603,13 @@ int fg_maxpool2_bwd(fg_view src, fg_view g_pooled, fg_view g_src, unsigned char*
 long long fg_bce_logits_workspace_doubles(void);
 int fg_bce_logits(fg_view logits, const float* target, float gscale, fg_view grad, float* loss, long long* correct,
                   double* work, hipStream_t stream);
+/* fg_bce_logits against the flood mask of a second logits view of the same grid: t = flood(ref_logits) ? 1 : 0,
+ * decided by the device function fg_mask_confusion and the renderer decide with (sigmoid(r) > 0.5 in fp32).  loss and
+ * grad as fg_bce_logits.  result: 16 bytes, 8-byte aligned -- the fp32 loss in the low half, and in the high half the
+ * int64 number of pixels whose own flood decision equals t (= tp + tn of fg_mask_confusion on the same two views).
+ * work: fg_bce_logits_workspace_doubles() doubles. */
+int fg_flood_mask_bce(fg_view logits, fg_view ref_logits, float gscale, fg_view grad, void* result, double* work,
+                      hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------- */
 /* evaluation metrics (models/model.py:363-422, models/group.py:114-221) */
@@ -601,6 +617,12 @@ int fg_bce_logits(fg_view logits, const float* target, float gscale, fg_view gra
 /* torch.clamp((src + 1) * 0.5, 0, 1) of an [n, c, h, w] (strided) generator output into dst (contiguous
  * NCHW, optional) and into buf's interior channels 0..c-1 (NHWC, optional: the segmentation U-Net's input). */
 int fg_unit_image(fg_sview src, int n, int c, int h, int w, float* dst, fg_view buf, hipStream_t stream);
+/* Backward of fg_unit_image: dst[n, ch, y, x] = scale * 0.5 * g(n, y, x, ch) * gate (added to dst when accumulate),
+ * g the gradient of the U-Net input (NHWC, c_alloc >= c), src the image the forward read, dst an [n, c, h, w] fp32
+ * tensor addressed by strides.  gate = 1 where the fp32 value v = (src + 1) * 0.5 satisfies 0 <= v <= 1 (both ends
+ * inclusive, as ATen's clamp backward), else 0 -- also for NaN. */
+int fg_unit_image_bwd(fg_view g, fg_sview src, int n, int c, int h, int w, float scale, fg_wview dst, int accumulate,
+                      hipStream_t stream);
 /* SSIM of two contiguous NCHW [n, c, h, w] images in [0, 1] (torchmetrics 1.2.0 _ssim_update: gaussian
  * 11x11 window gauss11 (normalised 1-D taps), constants c1 = (0.01 dr)^2, c2 = (0.03 dr)^2; the mean runs
  * over channels and the (h-10) x (w-10) windows inside the image): ssim[i], cs[i] (each optional) = per
