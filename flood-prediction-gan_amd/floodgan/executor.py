@@ -3,7 +3,8 @@
 These run the whole network as a fixed sequence of libfloodgan kernels over NHWC buffers
 (floodgan.plans.Buf), saving exactly the activations the explicit backward needs.  Both the
 autograd-facing drop-in modules (floodgan.model_architectures) and the fused training step
-(floodgan.model.paired_step) are built on them.
+(floodgan.model.PairedStep) are built on them.  The conv launches come from the layer kit (floodgan.layers); the
+discriminator is floodgan.patchgan's PatchGAN with InstanceNorm.
 
 Reference: models/model_architectures.py:339-400 (generator forward), :412-418 (resnet
 block), :424-441 (discriminator); backward = autograd of those graphs.
@@ -12,11 +13,12 @@ import os
 
 import torch
 
-from . import _lib as L
 from . import ops
 from . import opstate
+from . import patchgan
 from . import plans as PL
 from ._lib import FG_ACT_LRELU, FG_ACT_NONE, FG_ACT_RELU, FG_PAD_REFLECT, FG_PAD_ZERO, require_device
+from .layers import Grads, conv_fwd, convT_bwd, convT_fwd, decided, dgrad_s1, dgrad_s2, quad, quad_ok, wgrad_conv
 from .plans import Buf
 
 N_BLOCKS = 9
@@ -51,87 +53,18 @@ DISC_LAYERS = ["model.0", "model.2", "model.5", "model.8", "model.11"]
 D0_DGRAD = os.environ.get("FLOODGAN_D0_DGRAD", "1") != "0"
 
 
+# the kit's helpers under the names this module had them by: tests/test_gpu_parity.py calls them so
+_conv_fwd, _dgrad_s2, _quad_ok, _quad = conv_fwd, dgrad_s2, quad_ok, quad
+
+
 def disc_bucket_names():
     """the discriminator's gradient buckets (one per layer) in the order disc_backward completes them"""
     return [[f"{layer}.{k}" for k in ("weight", "bias")] for layer in reversed(DISC_LAYERS)]
 
 
-class _Grads:
-    """Destination of parameter gradients: either fresh tensors (autograd path) or
-    preallocated .grad tensors (fused step).
-
-    Every launch runs on the caller's (current) stream.  Weight gradients on a second stream beside the
-    input-gradient chain were measured slower (profiles/round2/r2m_*: 57.3 vs 56.6 ms per step; the
-    pipelined convs already hold every CU, so the overlapped kernels each slow down by the same factor)
-    and that path was removed in round 5."""
-
-    def __init__(self, params, into=None, accumulate=False, device=None):
-        self.params, self.into = params, into
-        self.acc = accumulate       # raise existing gradients (a network used several times per step)
-        self.out = {}
-
-    def get(self, name):
-        if name not in self.out:
-            p = self.params[name]
-            if self.into is not None and name in self.into:
-                self.out[name] = self.into[name]
-            else:
-                self.out[name] = torch.empty_like(p)
-        return self.out[name]
-
-    def off_path(self, fn, bufs, names=(), prepare=None):
-        """run fn() (weight-gradient launches reading the Bufs `bufs`, writing the gradients `names`)"""
-        for n in names:
-            self.get(n)
-        return fn()
-
-    def wgrad(self, prob, wmap, name, bufs, tag=None):
-        self.off_path(lambda: ops.wgrad(prob, wmap, self.get(name), accumulate=self.acc, tag=tag), bufs, (name,),
-                      prepare=lambda: ops.prepare_wgrad(prob))
-
-    def ready(self, ready, name):
-        return ready(name)
-
-    def join(self):
-        pass
-
-
 # ======================================================================================
 # generator
 # ======================================================================================
-
-def _conv_fwd(P, name, X, pad, k, stride, Y, act=FG_ACT_NONE, tag=None, in_stats=False):
-    """returns the InstanceNorm statistics of Y from the conv's epilogue when in_stats and available"""
-    w = P[name + ".weight"]
-    m = PL.wmap_conv_fwd(w.shape, X.c)
-    return ops.conv([PL.conv_problem(X, pad, k, stride, ops.pack_weight(w, m), m, Y, bias=P[name + ".bias"],
-                                     act=act)], tag=tag, in_stats=in_stats)
-
-
-# round 5: the four output phases of a stride-2, 3-tap transposed op with 64 output channels as ONE problem (the quad
-# form, plans.quad_map): each input pixel gathered once for all phases, zero segments skipped in the kernel.  The
-# FLOODGAN_QUAD=0 switch was retired in round 6: the four-phase problems remain for every other shape, and
-# tests/test_gpu_parity.py::test_quad_convT checks the quad form against fp64.
-def _quad_ok(X, shape, k, Y):
-    return (k == 3 and shape[1] == 64 and isinstance(Y, Buf) and Y.c == 64 and ops.is_presplit(X)
-            and L.fwd_f16x3() and (Y.h, Y.w, Y.n) == (2 * X.h, 2 * X.w, X.n) and X.pad >= 1 and X.c % 32 == 0
-            and X.c & (X.c - 1) == 0)
-
-
-def _quad(P, name, X, Y, bias=None, in_stats=False):
-    w = P[name + ".weight"]
-    m, d0, mask = PL.quad_map(w.shape, 3, 1, X.c)
-    return ops.conv([PL.quad_problem(X, m, d0, mask, ops.pack_weight(w, m), Y, bias=bias)], in_stats=in_stats)
-
-
-def _convT_fwd(P, name, X, Y):
-    w = P[name + ".weight"]
-    if _quad_ok(X, w.shape, 3, Y):
-        return _quad(P, name, X, Y, bias=P[name + ".bias"], in_stats=True)
-    maps = PL.phase_maps(w.shape, 3, 1, X.c)
-    wps = [ops.pack_weight(w, m) for m, _, _ in maps]
-    return ops.conv(PL.phase_problems(X, w.shape, 3, 1, Y, wps, maps, bias=P[name + ".bias"]), in_stats=True)
-
 
 def _norm(c, act, pad, mode, residual=None, stats=None, presplit=False, ps_copy=False, splitpix=False):
     """InstanceNorm + activation of conv output c; stats = (mean, rstd) from the conv's epilogue, or
@@ -149,6 +82,11 @@ def _norm(c, act, pad, mode, residual=None, stats=None, presplit=False, ps_copy=
 
 # the content head's input is written in the window kernels' split layout by its norm pass (step 46.39 -> 46.19 ms,
 # profiles/round4/r4e_ab_splitpix.log; the fp32 + fg_split_pixels alternative was retired in round 6)
+
+
+def _convT_fwd(P, name, X, Y):
+    """a decoder deconv: ConvTranspose2d(3, 2, 1, 1) whose epilogue emits the next norm's statistics"""
+    return convT_fwd(P, name, X, Y, 3, 1, in_stats=True)
 
 
 def has_attention(P):
@@ -177,14 +115,14 @@ def gen_forward(P, x, save=True, x_extra=None):
     X0 = Buf.empty(N, H, W, Cin + Ce, 3, dev)
     ops.pack_input(x, Cin, x_extra, Ce, X0, 0, N, FG_PAD_REFLECT)             # F.pad(input, 3, reflect)
     c1 = Buf.empty(N, H, W, 64, 0, dev)
-    st = _conv_fwd(P, "conv1", X0, 3, 7, 1, c1, in_stats=True)
+    st = conv_fwd(P, "conv1", X0, 3, 7, 1, c1, in_stats=True)
     ps = ops.presplit_on()     # norm outputs read only by pipelined convs / weight gradients: FG_PRESPLIT
     m1, r1, a1 = _norm(c1, FG_ACT_RELU, 1, FG_PAD_ZERO, stats=st, presplit=ps)
     c2 = Buf.empty(N, H // 2, W // 2, 128, 0, dev)
-    st = _conv_fwd(P, "conv2", a1, 1, 3, 2, c2, in_stats=True)
+    st = conv_fwd(P, "conv2", a1, 1, 3, 2, c2, in_stats=True)
     m2, r2, a2 = _norm(c2, FG_ACT_RELU, 1, FG_PAD_ZERO, stats=st, presplit=ps)
     c3 = Buf.empty(N, H // 4, W // 4, 256, 0, dev)
-    st = _conv_fwd(P, "conv3", a2, 1, 3, 2, c3, in_stats=True)
+    st = conv_fwd(P, "conv3", a2, 1, 3, 2, c3, in_stats=True)
     # block inputs / outputs: fp32 (the residual stream) and a pre-split copy for the convs that read them
     m3, r3, h, h_ps = _norm(c3, FG_ACT_RELU, 1, FG_PAD_REFLECT, stats=st, ps_copy=True)
     S.update(x=x, X0=X0, cin=Cin + Ce, c1=c1, m1=m1, r1=r1, a1=a1, c2=c2, m2=m2, r2=r2, a2=a2, c3=c3, m3=m3, r3=r3)
@@ -219,7 +157,7 @@ def gen_forward(P, x, save=True, x_extra=None):
             md2, rd2, ad2 = _norm(d2, FG_ACT_RELU, pad2, mode2, stats=st, splitpix=spx)
         heads[tag] = dict(d1=d1, md1=md1, rd1=rd1, ad1=ad1, d2=d2, md2=md2, rd2=rd2, ad2=ad2)
     cl = Buf.empty(N, H, W, CONTENT_ALLOC, 0, dev)
-    _conv_fwd(P, "deconv3_content", heads["content"]["ad2"], 3, 7, 1, cl)
+    conv_fwd(P, "deconv3_content", heads["content"]["ad2"], 3, 7, 1, cl)
     out = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
     if not attention:                                 # CycleGAN: nn.Tanh() on the 3 logits (:115-117)
         ops.tanh_head_fwd(cl, 3, out)
@@ -244,11 +182,11 @@ def _block_fwd(P, pre, h, out_mode, h_ps=None):
     N, Hh, Ww, Cc = h.n, h.h, h.w, h.c
     dev = h.t.device
     cb1 = Buf.empty(N, Hh, Ww, Cc, 0, dev)
-    st = _conv_fwd(P, pre + "conv1", h if h_ps is None else h_ps, 1, 3, 1, cb1, tag="resblock_conv_fwd", in_stats=True)
+    st = conv_fwd(P, pre + "conv1", h if h_ps is None else h_ps, 1, 3, 1, cb1, tag="resblock_conv_fwd", in_stats=True)
     # rb is read only by conv2 and conv2's weight gradient: pre-split for both (ops.PRESPLIT)
     mb1, rb1, rb = _norm(cb1, FG_ACT_RELU, 1, FG_PAD_REFLECT, stats=st, presplit=ops.presplit_on())
     cb2 = Buf.empty(N, Hh, Ww, Cc, 0, dev)
-    st = _conv_fwd(P, pre + "conv2", rb, 1, 3, 1, cb2, tag="resblock_conv_fwd", in_stats=True)
+    st = conv_fwd(P, pre + "conv2", rb, 1, 3, 1, cb2, tag="resblock_conv_fwd", in_stats=True)
     if h_ps is None:          # a lone block (block_forward_nchw): no copies
         mb2, rb2, hn = _norm(cb2, FG_ACT_NONE, 1, out_mode, residual=h, stats=st)
         hn_ps = None
@@ -262,7 +200,7 @@ def _block_bwd(P, pre, b, grad, G):
     (gsrc, fold_pad, gadd): the gradient is fold(gsrc) + gadd -- the next block's input gradient is the
     reflect-pad adjoint of its conv1 input gradient plus the residual path's gradient, and its norm
     backward's statistics pass gathers that sum directly (and writes it out once, for this block's own
-    residual path: gsum), so no separate fold + add pass runs.  The caller joins G's side stream."""
+    residual path: gsum), so no separate fold + add pass runs."""
     gsrc, fold, gadd = grad
     cb2 = b["cb2"]
     N, Hh, Ww, Cc = cb2.n, cb2.h, cb2.w, cb2.c
@@ -274,12 +212,12 @@ def _block_bwd(P, pre, b, grad, G):
     ps = ops.presplit_on()
     ops.in_bwd(gsrc, fold, gadd, cb2, b["mb2"], b["rb2"], FG_ACT_NONE, g_cb2, G.get(pre + "conv2.bias"), G.acc,
                gsum=g_h if lazy else None, presplit=ps)
-    _wgrad_conv(P, G, pre + "conv2", g_cb2, b["rb"], 1, 3, 1, tag="resblock_conv_wgrad")
+    wgrad_conv(P, G, pre + "conv2", g_cb2, b["rb"], 1, 3, 1, tag="resblock_conv_wgrad")
     g_rbp = _dgrad_s1_padded(P, pre + "conv2", g_cb2)  # gradient w.r.t. the reflect-padded relu output
     g_cb1 = Buf.empty(N, Hh, Ww, Cc, 2, dev)
     ops.in_bwd(g_rbp, 1, None, b["cb1"], b["mb1"], b["rb1"], FG_ACT_RELU, g_cb1, G.get(pre + "conv1.bias"), G.acc,
                presplit=ps)
-    _wgrad_conv(P, G, pre + "conv1", g_cb1, b["h"] if b.get("h_ps") is None else b["h_ps"], 1, 3, 1,
+    wgrad_conv(P, G, pre + "conv1", g_cb1, b["h"] if b.get("h_ps") is None else b["h_ps"], 1, 3, 1,
                 tag="resblock_conv_wgrad")
     g_hp = _dgrad_s1_padded(P, pre + "conv1", g_cb1)
     return g_hp, 1, g_h                               # reflect-pad adjoint + residual path, summed lazily
@@ -334,36 +272,13 @@ def block_backward_nchw(S, g, need_input=True):
     N, Cc, Hh, Ww = g.shape
     gb = Buf.empty(N, Hh, Ww, Cc, 0, g.device)
     ops.pack_input(g, Cc, None, 0, gb, 0, N, FG_PAD_ZERO)
-    G = _Grads(S["P"], device=g.device)
+    G = Grads(S["P"])
     g_hp, fold, g_res = _block_bwd(S["P"], "", S["b"], (gb, 0, None), G)
     g_new = Buf.empty(N, Hh, Ww, Cc, 0, g.device)
     ops.fold_add(g_hp, fold, g_res, g_new)
-    G.join()
     grads = {"w1": G.out["conv1.weight"], "b1": G.out["conv1.bias"],
              "w2": G.out["conv2.weight"], "b2": G.out["conv2.bias"]}
     return (_to_nchw(g_new) if need_input else None), grads
-
-
-def _wgrad_conv(P, G, name, gy, X, pad, k, stride, tag=None):
-    w = P[name + ".weight"]
-    G.wgrad(PL.wgrad_conv(gy, X, pad, k, stride, w.shape[0]), PL.wmap_wgrad(w.shape, True, X.c, k), name + ".weight",
-            (gy, X), tag=tag)
-
-
-def _dgrad_s1(P, name, gyp, pad_used, k, Y):
-    w = P[name + ".weight"]
-    m = PL.wmap_conv_dgrad_s1(w.shape, gyp.c)
-    ops.conv([PL.conv_problem(gyp, pad_used, k, 1, ops.pack_weight(w, m), m, Y)])
-
-
-def _dgrad_s2(P, name, gy, k, Y=None, y_nchw=None, n_base=0, n_out=None, accumulate=0):
-    w = P[name + ".weight"]
-    if y_nchw is None and not n_base and n_out is None and not accumulate and _quad_ok(gy, w.shape, k, Y):
-        _quad(P, name, gy, Y)
-        return
-    maps = PL.phase_maps(w.shape, k, 1, gy.c, n_base=n_base, n_out=n_out)
-    wps = [ops.pack_weight(w, m) for m, _, _ in maps]
-    ops.conv(PL.phase_problems(gy, w.shape, k, 1, Y, wps, maps, y_nchw=y_nchw, accumulate=accumulate))
 
 
 G_BUCKETS = ([f"{h}_{t}" for t in ("content", "attention") for h in ("deconv1", "deconv2", "deconv3")],) + \
@@ -394,7 +309,7 @@ def gen_backward(P, S, g_out, grads_into=None, ready=None, input_grad=None, accu
     loss that reads the mask (models/model_architectures.py:396 keeps it in the autograd graph)."""
     ready = ready or (lambda name: None)
     x = S["x"]
-    G = _Grads(P, grads_into, accumulate, device=x.device)
+    G = Grads(P, grads_into, accumulate)
     assert not accumulate or grads_into is not None
     N, _, H, W = x.shape
     Cin = S["cin"]             # input channels, including a fused x_extra
@@ -415,19 +330,18 @@ def gen_backward(P, S, g_out, grads_into=None, ready=None, input_grad=None, accu
         assert g_mask is None, "the CycleGAN generator has no attention mask"
         ops.tanh_head_bwd(cl, 3, g_out, gcl)
     # ---- deconv3_content: 7x7 over reflect-padded (3) ad2
-    _wgrad_conv(P, G, "deconv3_content", gcl, hc["ad2"], 3, 7, 1)
+    wgrad_conv(P, G, "deconv3_content", gcl, hc["ad2"], 3, 7, 1)
     ops.channel_sum(gcl, n_content, G.get("deconv3_content.bias"), G.acc)
     g_ad2c = Buf.empty(N, H + 6, W + 6, 64, 0, dev)     # gradient w.r.t. the PADDED input
-    _dgrad_s1(P, "deconv3_content", gcl, 6, 7, g_ad2c)
+    dgrad_s1(P, "deconv3_content", gcl, 6, 7, g_ad2c)
     heads = [("content", hc, g_ad2c, 3)]
     if attention:
         # ---- deconv3_attention: 1x1
         # the fused head: weight, bias and input gradients in its norm backward below (g_ad2a None)
         g_ad2a = None if FUSED_HEAD else Buf.empty(N, H, W, 64, 0, dev)
         if g_ad2a is not None:
-            names = ("deconv3_attention.weight", "deconv3_attention.bias")
-            G.off_path(lambda: ops.conv1x1_wgrad(gal, ha["ad2"], N_ATT, G.get(names[0]), G.get(names[1]), G.acc),
-                       (gal, ha["ad2"]), names)
+            ops.conv1x1_wgrad(gal, ha["ad2"], N_ATT, G.get("deconv3_attention.weight"),
+                              G.get("deconv3_attention.bias"), G.acc)
             ops.conv1x1_dgrad(gal, P["deconv3_attention.weight"], N_ATT, g_ad2a)
         heads.append(("attention", ha, g_ad2a, 0))
     # ---- deconv2 / deconv1 of both heads
@@ -443,84 +357,56 @@ def gen_backward(P, S, g_out, grads_into=None, ready=None, input_grad=None, accu
         else:
             ops.in_bwd(g_ad2, fold, None, hd["d2"], hd["md2"], hd["rd2"], FG_ACT_RELU, g_d2,
                        G.get(f"deconv2_{tag}.bias"), G.acc, presplit=ps)
-        name = f"deconv2_{tag}"
-        w = P[name + ".weight"]
-        G.wgrad(PL.wgrad_convT(hd["ad1"], g_d2, 3, 1, w.shape[0]), PL.wmap_wgrad(w.shape, True, g_d2.c, 3),
-                name + ".weight", (hd["ad1"], g_d2))
         g_ad1 = Buf.empty(N, H // 2, W // 2, 128, 0, dev)
-        m = PL.wmap_convT_dgrad(w.shape, g_d2.c)
-        ops.conv([PL.conv_problem(g_d2, 1, 3, 2, ops.pack_weight(w, m), m, g_ad1)])
+        convT_bwd(P, G, f"deconv2_{tag}", hd["ad1"], g_d2, 3, 1, g_ad1)
         g_d1 = Buf.empty(N, H // 2, W // 2, 128, 1, dev)
         ops.in_bwd(g_ad1, 0, None, hd["d1"], hd["md1"], hd["rd1"], FG_ACT_RELU, g_d1, G.get(f"deconv1_{tag}.bias"),
                    G.acc, presplit=ps)
-        name = f"deconv1_{tag}"
-        w = P[name + ".weight"]
         hx = S["h"] if S.get("h_ps") is None else S["h_ps"]
-        G.wgrad(PL.wgrad_convT(hx, g_d1, 3, 1, w.shape[0]), PL.wmap_wgrad(w.shape, True, g_d1.c, 3),
-                name + ".weight", (hx, g_d1))
-        m = PL.wmap_convT_dgrad(w.shape, g_d1.c)
-        ops.conv([PL.conv_problem(g_d1, 1, 3, 2, ops.pack_weight(w, m), m, g_h, accumulate=idx)])
-    G.ready(ready, "deconv1_content")
+        convT_bwd(P, G, f"deconv1_{tag}", hx, g_d1, 3, 1, g_h, accumulate=idx)   # both heads' gradients, summed
+    ready("deconv1_content")
     # ---- resnet blocks in reverse: out = h + IN(conv2(pad(relu(IN(conv1(pad(h)))))))
     grad = (g_h, 0, None)
     for i in reversed(range(N_BLOCKS)):
         grad = _block_bwd(P, f"resnet_blocks.{i}.", S["blocks"][i], grad, G)
-        G.ready(ready, _blk(i, 1))
+        ready(_blk(i, 1))
     # ---- encoder (the first block's input gradient, fold + residual, gathered by conv3's norm backward)
     g_c3 = Buf.empty(N, H // 4, W // 4, 256, 1, dev)
     ops.in_bwd(grad[0], grad[1], grad[2], S["c3"], S["m3"], S["r3"], FG_ACT_RELU, g_c3, G.get("conv3.bias"), G.acc,
                presplit=ps)
-    _wgrad_conv(P, G, "conv3", g_c3, S["a2"], 1, 3, 2)
+    wgrad_conv(P, G, "conv3", g_c3, S["a2"], 1, 3, 2)
     g_a2 = Buf.empty(N, H // 2, W // 2, 128, 0, dev)
-    _dgrad_s2(P, "conv3", g_c3, 3, Y=g_a2)
+    dgrad_s2(P, "conv3", g_c3, 3, Y=g_a2)
     g_c2 = Buf.empty(N, H // 2, W // 2, 128, 1, dev)
     ops.in_bwd(g_a2, 0, None, S["c2"], S["m2"], S["r2"], FG_ACT_RELU, g_c2, G.get("conv2.bias"), G.acc, presplit=ps)
-    _wgrad_conv(P, G, "conv2", g_c2, S["a1"], 1, 3, 2)
+    wgrad_conv(P, G, "conv2", g_c2, S["a1"], 1, 3, 2)
     g_a1 = Buf.empty(N, H, W, 64, 0, dev)
-    _dgrad_s2(P, "conv2", g_c2, 3, Y=g_a1)
+    dgrad_s2(P, "conv2", g_c2, 3, Y=g_a1)
     # zero border 6 = the full correlation of the 7x7 stem when the input gradient is wanted
     g_c1 = Buf.empty(N, H, W, 64, 0 if input_grad is None else 6, dev)
     ops.in_bwd(g_a1, 0, None, S["c1"], S["m1"], S["r1"], FG_ACT_RELU, g_c1, G.get("conv1.bias"), G.acc)
-    _wgrad_conv(P, G, "conv1", g_c1, S["X0"], 3, 7, 1)
-    G.ready(ready, "conv1")
+    wgrad_conv(P, G, "conv1", g_c1, S["X0"], 3, 7, 1)
+    ready("conv1")
     if input_grad is not None:
         # gradient of the reflect-padded input (9 -> 12 channels: aligned rows), then the pad's
         # adjoint into NCHW, accumulated onto the tail's x[:, :3] term
         g_x0 = Buf.empty(N, H + 6, W + 6, PL.rup(Cin, 4), 0, dev)
-        _dgrad_s1(P, "conv1", g_c1, 6, 7, g_x0)
+        dgrad_s1(P, "conv1", g_c1, 6, 7, g_x0)
         ops.unfold_nchw(g_x0, 3, Cin, input_grad, acc_channels=3 if attention else 0)
-    G.join()
     return G.out
-
-
-def _decided(B, lo=0, hi=None, pre=None, mean=None):
-    """activation decisions of an activation-output Buf (output > 0 <=> input > 0 for ReLU and
-    LeakyReLU): NCHW bool on the host.  A pre-split output (FG_PRESPLIT) is decided from the norm's input
-    `pre` and `mean` instead: act((c - mean) * rstd) > 0 <=> c > mean (rstd > 0; fp32 subtraction keeps the
-    sign)."""
-    if B is None or ops.is_presplit(B) or ops.is_splitpix(B):     # (None: the fused head's unwritten activation)
-        d = pre.interior() > mean.view(pre.n, 1, 1, pre.c)
-        return d[lo:hi].permute(0, 3, 1, 2).contiguous().cpu()
-    return (B.interior()[lo:hi] > 0).permute(0, 3, 1, 2).contiguous().cpu()
 
 
 def gen_act_decisions(S):
     """The generator's ReLU decisions in a saved forward, keyed by the oracle's layer names (test
     instrumentation: oracle ActDecisions teacher-forces them to compare gradients at full size)."""
-    out = {"conv1": _decided(S["a1"], pre=S["c1"], mean=S["m1"]), "conv2": _decided(S["a2"], pre=S["c2"], mean=S["m2"]),
-           "conv3": _decided(S["blocks"][0]["h"])}
+    out = {"conv1": decided(S["a1"], pre=S["c1"], mean=S["m1"]), "conv2": decided(S["a2"], pre=S["c2"], mean=S["m2"]),
+           "conv3": decided(S["blocks"][0]["h"])}
     for i, b in enumerate(S["blocks"]):
-        out[f"block{i}"] = _decided(b["rb"], pre=b["cb1"], mean=b["mb1"])
+        out[f"block{i}"] = decided(b["rb"], pre=b["cb1"], mean=b["mb1"])
     for tag, hd in S["heads"].items():
-        out[f"deconv1_{tag}"] = _decided(hd["ad1"], pre=hd["d1"], mean=hd["md1"])
-        out[f"deconv2_{tag}"] = _decided(hd["ad2"], pre=hd["d2"], mean=hd["md2"])
+        out[f"deconv1_{tag}"] = decided(hd["ad1"], pre=hd["d1"], mean=hd["md1"])
+        out[f"deconv2_{tag}"] = decided(hd["ad2"], pre=hd["d2"], mean=hd["md2"])
     return out
-
-
-def disc_act_decisions(S, lo=0, hi=None):
-    """The discriminator's LeakyReLU decisions for images lo..hi of a saved forward (test instrumentation)"""
-    return {"model.0": _decided(S["e0"], lo, hi), "model.2": _decided(S["a1"], lo, hi, S["e1"], S["m1"]),
-            "model.5": _decided(S["a2"], lo, hi, S["e2"], S["m2"]), "model.8": _decided(S["a3"], lo, hi)}
 
 
 # ======================================================================================
@@ -554,105 +440,33 @@ def disc_prefix(buf, n):
     return v
 
 
+class DiscInstanceNorm:
+    """patchgan's norm object: InstanceNorm + LeakyReLU on the conv epilogue's statistics; the conv's bias gradient
+    comes out of the norm backward"""
+
+    conv_stats = True
+
+    def forward(self, P, conv, e, stats, fp32):
+        # the activations read only by pipelined convs / weight gradients: FG_PRESPLIT (not the fp32 head kernel's)
+        mean, rstd, a = _norm(e, FG_ACT_LRELU, 1, FG_PAD_ZERO, stats=stats, presplit=ops.presplit_on() and not fp32)
+        return dict(e=e, mean=mean, rstd=rstd, a=a)
+
+    def backward(self, P, G, conv, L, g_a, g_e):
+        # the conv-output gradients feed only pipelined convs / weight gradients: pre-split
+        ops.in_bwd(g_a, 0, None, L["e"], L["mean"], L["rstd"], FG_ACT_LRELU, g_e,
+                   G.get(conv + ".bias") if G is not None else None, presplit=ops.presplit_on())
+
+
 def disc_forward(P, inp, save=True):
     """inp: Buf from disc_pack (zero border 1).  Returns (pred [N,1,ho,wo], saved)."""
-    N, H, W = inp.n, inp.h, inp.w
-    dev = inp.t.device
-    if H < 24 or W < 24:
-        raise RuntimeError(f"PairedAttentionDiscriminator needs H, W >= 24 (got {H}x{W})")
-    h1, w1 = PL.out_size(H, 4, 2, 1), PL.out_size(W, 4, 2, 1)
-    e0 = Buf.empty(N, h1, w1, 64, 1, dev)              # conv + bias + LeakyReLU fused, zero border
-    _conv_fwd(P, "model.0", inp, 1, 4, 2, e0, act=FG_ACT_LRELU)
-    ops.zero_border(e0)
-    h2, w2 = PL.out_size(h1, 4, 2, 1), PL.out_size(w1, 4, 2, 1)
-    e1 = Buf.empty(N, h2, w2, 128, 0, dev)
-    st = _conv_fwd(P, "model.2", e0, 1, 4, 2, e1, in_stats=True)
-    ps = ops.presplit_on()     # a1, a2 are read only by pipelined convs / weight gradients: FG_PRESPLIT
-    m1, r1, a1 = _norm(e1, FG_ACT_LRELU, 1, FG_PAD_ZERO, stats=st, presplit=ps)
-    h3, w3 = PL.out_size(h2, 4, 2, 1), PL.out_size(w2, 4, 2, 1)
-    e2 = Buf.empty(N, h3, w3, 256, 0, dev)
-    st = _conv_fwd(P, "model.5", a1, 1, 4, 2, e2, in_stats=True)
-    m2, r2, a2 = _norm(e2, FG_ACT_LRELU, 1, FG_PAD_ZERO, stats=st, presplit=ps)
-    h4, w4 = PL.out_size(h3, 4, 1, 1), PL.out_size(w3, 4, 1, 1)
-    e3 = Buf.empty(N, h4, w4, 512, 0, dev)
-    st = _conv_fwd(P, "model.8", a2, 1, 4, 1, e3, in_stats=True)
-    m3, r3, a3 = _norm(e3, FG_ACT_LRELU, 1, FG_PAD_ZERO, stats=st)
-    h5, w5 = PL.out_size(h4, 4, 1, 1), PL.out_size(w4, 4, 1, 1)
-    pred = torch.empty(N, 1, h5, w5, dtype=torch.float32, device=dev)
-    ops.conv_n1_fwd(a3, P["model.11.weight"], P["model.11.bias"], pred)      # GEMV-shaped: fp32 FMA kernel
-    S = dict(inp=inp, e0=e0, e1=e1, m1=m1, r1=r1, a1=a1, e2=e2, m2=m2, r2=r2, a2=a2, e3=e3, m3=m3, r3=r3, a3=a3)
-    return pred, (S if save else None)
+    return patchgan.forward(P, inp, DiscInstanceNorm(), save, "PairedAttentionDiscriminator")
 
 
 def disc_backward(P, S, g_pred, param_grads=True, grads_into=None, input_grad=None, input_grad_channels=None,
                   input_grad_accumulate=False, ready=None):
-    """Explicit backward of disc_forward.
-    param_grads: compute weight / bias gradients (False in the generator step, where D is
-    frozen: models/model.py:636-637).  input_grad: contiguous NCHW tensor whose channels 0 .. count
-    receive dL/d(input channels input_grad_channels=(start, count)), written or accumulated.  ready(layer name), when
-    given, is called as each layer's gradients are complete (parallel.FlatGrads buckets)."""
-    ready = (ready if param_grads and ready is not None else (lambda name: None))
-    inp = S["inp"]
-    N = inp.n
-    dev = inp.t.device
-    G = _Grads(P, grads_into, device=dev)
-    a3 = S["a3"]
-    h5, w5 = g_pred.shape[2], g_pred.shape[3]
-    g11 = Buf.empty(N, h5, w5, 1, 3, dev)              # zero border 3: the n1 weight-gradient kernel's reach
-    ops.pack_input(g_pred, 1, None, 0, g11, 0, N, FG_PAD_ZERO)
-    if param_grads:
-        w11 = P["model.11.weight"]
-        G.off_path(lambda: ops.conv_n1_wgrad(a3, g11, PL.wmap_wgrad(w11.shape, True, a3.c, 4),
-                                             G.get("model.11.weight")), (a3, g11), ("model.11.weight",))   # fp32
-        ops.channel_sum(g11, 1, G.get("model.11.bias"))
-        G.ready(ready, "model.11")
-    g_a3 = Buf.empty(N, a3.h, a3.w, 512, 0, dev)
-    _dgrad_s1(P, "model.11", g11, 2, 4, g_a3)
-    # model.8 (k4 s1 p1) + IN + LReLU
-    g_e3 = Buf.empty(N, a3.h, a3.w, 512, 2, dev)
-    ps = ops.presplit_on()     # the conv-output gradients feed only pipelined convs / weight gradients
-    ops.in_bwd(g_a3, 0, None, S["e3"], S["m3"], S["r3"], FG_ACT_LRELU, g_e3,
-               G.get("model.8.bias") if param_grads else None, presplit=ps)
-    a2 = S["a2"]
-    if param_grads:
-        _wgrad_conv(P, G, "model.8", g_e3, a2, 1, 4, 1)
-        G.ready(ready, "model.8")
-    g_a2 = Buf.empty(N, a2.h, a2.w, 256, 0, dev)
-    _dgrad_s1(P, "model.8", g_e3, 2, 4, g_a2)
-    # model.5 (k4 s2 p1)
-    g_e2 = Buf.empty(N, a2.h, a2.w, 256, 1, dev)
-    ops.in_bwd(g_a2, 0, None, S["e2"], S["m2"], S["r2"], FG_ACT_LRELU, g_e2,
-               G.get("model.5.bias") if param_grads else None, presplit=ps)
-    a1 = S["a1"]
-    if param_grads:
-        _wgrad_conv(P, G, "model.5", g_e2, a1, 1, 4, 2)
-        G.ready(ready, "model.5")
-    g_a1 = Buf.empty(N, a1.h, a1.w, 128, 0, dev)
-    _dgrad_s2(P, "model.5", g_e2, 4, Y=g_a1)
-    # model.2
-    g_e1 = Buf.empty(N, a1.h, a1.w, 128, 1, dev)
-    ops.in_bwd(g_a1, 0, None, S["e1"], S["m1"], S["r1"], FG_ACT_LRELU, g_e1,
-               G.get("model.2.bias") if param_grads else None, presplit=ps)
-    e0 = S["e0"]
-    if param_grads:
-        _wgrad_conv(P, G, "model.2", g_e1, e0, 1, 4, 2)
-        G.ready(ready, "model.2")
-    g_e0 = Buf.empty(N, e0.h, e0.w, 64, 1, dev)
-    _dgrad_s2(P, "model.2", g_e1, 4, Y=g_e0)
-    ops.zero_border(g_e0)
-    ops.act_bwd(Buf(g_e0.t, N, e0.h, e0.w, 64, 1), e0, FG_ACT_LRELU, border_zero=True)   # LeakyReLU of model.1
-    if param_grads:
-        _wgrad_conv(P, G, "model.0", g_e0, inp, 1, 4, 2)
-        ops.channel_sum(g_e0, 64, G.get("model.0.bias"))
-        G.ready(ready, "model.0")
-    if input_grad is not None:
-        c0, cn = input_grad_channels
-        # input_grad: contiguous [N, Ctot, H, W]; D-input channels c0 .. c0+cn land in its channels 0 .. cn
-        assert input_grad.is_contiguous() and input_grad.shape[1] >= cn
-        if D0_DGRAD and ops.d0_input_grad_ok(g_e0, c0, cn, inp.h, inp.w):
-            ops.d0_input_grad(g_e0, P["model.0.weight"], c0, cn, input_grad, input_grad_accumulate)
-        else:
-            _dgrad_s2(P, "model.0", g_e0, 4, y_nchw=(input_grad.view(-1), input_grad.shape[1], inp.h, inp.w),
-                      n_base=c0, n_out=cn, accumulate=int(input_grad_accumulate))
-    G.join()
-    return G.out
+    """Explicit backward of disc_forward (patchgan.backward documents the arguments)."""
+    return patchgan.backward(P, S, g_pred, param_grads, grads_into, input_grad, input_grad_channels,
+                             input_grad_accumulate, ready, raise_e0_slot=True, d0_fast=D0_DGRAD)
+
+
+disc_act_decisions = patchgan.act_decisions

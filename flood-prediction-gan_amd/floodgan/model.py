@@ -46,8 +46,8 @@ class PairedStep:
         self.gp, self.dp = generator.param_dict(), discriminator.param_dict()
         # gradient buffers laid out in the order the backward completes them: each bucket's RCCL
         # all-reduce starts as soon as it is written and overlaps the rest of the backward
-        self.gflat = FlatGrads(self.gp, X.gen_bucket_names())
-        self.dflat = FlatGrads(self.dp, X.disc_bucket_names())
+        self.gflat = FlatGrads(self.gp, self._net.gen_bucket_names())
+        self.dflat = FlatGrads(self.dp, self._net.disc_bucket_names())
         self.group = group
         self.last_mask = None
         self.last_output = None
@@ -62,29 +62,44 @@ class PairedStep:
         self.d_after = None
         self.d_after_own = None
 
+    # ---- the networks: what a subclass running the same iteration on other executors overrides.  _net is the
+    # executor module, for what both spell alike (bucket orders, gen_backward, disc_backward, *_act_decisions);
+    # the two forwards take different arguments
+    _net = X
+
+    def _gen_forward(self, x):
+        """-> (fake, attention mask or None, saved)"""
+        return X.gen_forward(self.gp, x, save=True)
+
+    def _disc_forward(self, dinp, groups):
+        """groups: the separate discriminator calls of the reference stacked along dinp's batch"""
+        return X.disc_forward(self.dp, dinp, save=True)      # InstanceNorm is per sample: one batch is the same
+
     def __call__(self, x, y):
         ws, _ = world()
         inv = 1.0 / ws
-        N = x.shape[0]
+        N, C, H, W = x.shape
         dev = x.device
-        C = x.shape[1]
         losses = torch.empty(4, dtype=torch.float32, device=dev)
         # (the flat gradient views are attached right before each backward: the per-parameter checks then run on
         # the host while the GPU works through the forward instead of ahead of the step's first launch)
         # generator forward                                           (models/model.py:615)
-        fake, mask, gS = X.gen_forward(self.gp, x, save=True)
+        fake, mask, gS = self._gen_forward(x)
         # ---- discriminator step: fake (detached) and real in one 2N batch   (:620-633)
         dinp = X.disc_pack([(x, fake), (x, y)], C + 3)
-        pred, dS = X.disc_forward(self.dp, dinp, save=True)
+        pred, dS = self._disc_forward(dinp, 2)
         g_pred = torch.empty_like(pred)
         ops.mse_const(pred[:N], 0.0, 0.5 * inv, losses[1:2], g_pred[:N])
         ops.mse_const(pred[N:], 1.0, 0.5 * inv, losses[0:1], g_pred[N:])
-        rec = {"G": [X.gen_act_decisions(gS)], "D": [X.disc_act_decisions(dS, 0, N), X.disc_act_decisions(dS, N)]} \
-            if self.record_decisions else None
+        net = self._net
+        rec = None
+        if self.record_decisions:
+            rec = {"G": [net.gen_act_decisions(gS)],
+                   "D": [net.disc_act_decisions(dS, 0, N), net.disc_act_decisions(dS, N)]}
         self.dflat.attach()
         self.dflat.begin(self.group)
-        X.disc_backward(self.dp, dS, g_pred, param_grads=True, grads_into=self._grads(self.dp),
-                        ready=self.dflat.ready)
+        net.disc_backward(self.dp, dS, g_pred, param_grads=True, grads_into=self._grads(self.dp),
+                          ready=self.dflat.ready)
         del dS
         self.dflat.finish()
         self.opt_d.step()
@@ -95,23 +110,23 @@ class PairedStep:
                     p.copy_(self.d_after[k])
         # ---- generator step against the updated discriminator                 (:636-646)
         dinp = X.disc_prefix(dinp, N)          # (x, fake): the D step's first half, unchanged since
-        pred, dS = X.disc_forward(self.dp, dinp, save=True)
+        pred, dS = self._disc_forward(dinp, 1)
         g_pred = torch.empty_like(pred)
         ops.mse_const(pred, 1.0, inv, losses[2:3], g_pred)
-        g_fake = torch.empty(N, 3, x.shape[2], x.shape[3], dtype=torch.float32, device=dev)
+        g_fake = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
         ops.l1(fake, y, 100.0 * inv, losses[3:4], g_fake, loss_scale=100.0)     # logged as 100 * L1 (:643-651)
         if self.fake_loss is not None:
             losses = torch.cat([losses, self.fake_loss(fake, y, g_fake, self.fake_loss.weight * inv)])
-        X.disc_backward(self.dp, dS, g_pred, param_grads=False, input_grad=g_fake, input_grad_channels=(C, 3),
-                        input_grad_accumulate=True)
+        net.disc_backward(self.dp, dS, g_pred, param_grads=False, input_grad=g_fake, input_grad_channels=(C, 3),
+                          input_grad_accumulate=True)
         if rec is not None:
-            rec["D"].append(X.disc_act_decisions(dS))
+            rec["D"].append(net.disc_act_decisions(dS))
             rec["L1"] = [{"l1": torch.sign(fake.detach() - y)}]   # the L1 term's sign decisions (-1 / 0 / +1)
             self.decisions = rec
         del dS, dinp
         self.gflat.attach()
         self.gflat.begin(self.group)
-        X.gen_backward(self.gp, gS, g_fake, grads_into=self._grads(self.gp), ready=self.gflat.ready)
+        net.gen_backward(self.gp, gS, g_fake, grads_into=self._grads(self.gp), ready=self.gflat.ready)
         del gS
         self.gflat.finish()
         self.opt_g.step()
@@ -130,18 +145,11 @@ class Pix2PixStep(PairedStep):
     updates the discriminator's running statistics a third time.  With dropout_rng "host" the generator's Dropout
     masks are torch's CPU stream in the reference's order, regenerated on the device (floodgan.torch_rng)."""
 
+    _net = P2P
+
     def __init__(self, generator, discriminator, opt_g, opt_d, group=None):
-        self.G, self.D = generator, discriminator
-        self.opt_g, self.opt_d = opt_g, opt_d
-        self.gp, self.dp = generator.param_dict(), discriminator.param_dict()
+        super().__init__(generator, discriminator, opt_g, opt_d, group)
         self.gb, self.db = generator.buffer_dict(), discriminator.buffer_dict()
-        self.gflat = FlatGrads(self.gp, P2P.gen_bucket_names())
-        self.dflat = FlatGrads(self.dp, P2P.disc_bucket_names())
-        self.group = group
-        self.last_mask = None
-        self.last_output = None
-        self.record_decisions = False
-        self.decisions = None
         self.masks = None        # test hook: dropout masks to use instead of drawing
         self.last_masks = None
 
@@ -156,58 +164,19 @@ class Pix2PixStep(PairedStep):
             masks = P2P.draw_dropout(N, H, W, self.G.dropout_rng, x.device)
         self.last_masks = masks
         try:
-            return self._iterate(x, y, masks)
+            return super().__call__(x, y)
         finally:
             # torch's CPU generator advanced past this iteration's Dropout draws -- also when the iteration raised
             # (its masks were drawn: a retry must not reuse them); commit() raises if anything drew in between
             if commit is not None:
                 commit()
 
-    def _iterate(self, x, y, masks):
-        ws, _ = world()
-        inv = 1.0 / ws
-        N, C, H, W = x.shape
-        dev = x.device
-        losses = torch.empty(4, dtype=torch.float32, device=dev)
-        fake, gS = P2P.gen_forward(self.gp, self.gb, x, masks=masks, training=True, save=True)
-        dinp = X.disc_pack([(x, fake), (x, y)], C + 3)
-        pred, dS = P2P.disc_forward(self.dp, self.db, dinp, groups=2, training=True, save=True)
-        g_pred = torch.empty_like(pred)
-        ops.mse_const(pred[:N], 0.0, 0.5 * inv, losses[1:2], g_pred[:N])
-        ops.mse_const(pred[N:], 1.0, 0.5 * inv, losses[0:1], g_pred[N:])
-        rec = {"G": [P2P.gen_act_decisions(gS)], "D": [P2P.disc_act_decisions(dS, 0, N),
-                                                       P2P.disc_act_decisions(dS, N)]} \
-            if self.record_decisions else None
-        self.dflat.attach()
-        self.dflat.begin(self.group)
-        P2P.disc_backward(self.dp, dS, g_pred, param_grads=True, grads_into=self._grads(self.dp),
-                          ready=self.dflat.ready)
-        del dS
-        self.dflat.finish()
-        self.opt_d.step()
-        dinp = X.disc_prefix(dinp, N)          # (x, fake): the D step's first half, unchanged since
-        pred, dS = P2P.disc_forward(self.dp, self.db, dinp, groups=1, training=True, save=True)
-        g_pred = torch.empty_like(pred)
-        ops.mse_const(pred, 1.0, inv, losses[2:3], g_pred)
-        g_fake = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
-        ops.l1(fake, y, 100.0 * inv, losses[3:4], g_fake, loss_scale=100.0)     # logged as 100 * L1 (:643-651)
-        if self.fake_loss is not None:
-            losses = torch.cat([losses, self.fake_loss(fake, y, g_fake, self.fake_loss.weight * inv)])
-        P2P.disc_backward(self.dp, dS, g_pred, param_grads=False, input_grad=g_fake, input_grad_channels=(C, 3),
-                          input_grad_accumulate=True)
-        if rec is not None:
-            rec["D"].append(P2P.disc_act_decisions(dS))
-            rec["L1"] = [{"l1": torch.sign(fake.detach() - y)}]   # the L1 term's sign decisions (-1 / 0 / +1)
-            self.decisions = rec
-        del dS, dinp
-        self.gflat.attach()
-        self.gflat.begin(self.group)
-        P2P.gen_backward(self.gp, gS, g_fake, grads_into=self._grads(self.gp), ready=self.gflat.ready)
-        del gS
-        self.gflat.finish()
-        self.opt_g.step()
-        self.last_output = fake
-        return losses
+    def _gen_forward(self, x):
+        fake, gS = P2P.gen_forward(self.gp, self.gb, x, masks=self.last_masks, training=True, save=True)
+        return fake, None, gS
+
+    def _disc_forward(self, dinp, groups):
+        return P2P.disc_forward(self.dp, self.db, dinp, groups=groups, training=True, save=True)
 
 
 class Model:

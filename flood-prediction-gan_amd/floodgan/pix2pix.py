@@ -1,5 +1,6 @@
 """Native forward / backward executors of the Pix2Pix U-Net-256 generator and its BatchNorm PatchGAN
-discriminator, and the fused Pix2Pix training iteration.
+discriminator; the fused iteration is floodgan.model.Pix2PixStep.  The conv launches come
+from the layer kit (floodgan.layers); the discriminator is floodgan.patchgan's PatchGAN with DiscBatchNorm.
 
 Reference: models/model_architectures.py:9-62 (Pix2PixGenerator / Pix2PixBlock), :64-85
 (Pix2PixDiscriminator), models/model.py:611-651 (train_paired, shared with PairedAttention).
@@ -33,11 +34,12 @@ updated twice, in order).
 """
 import torch
 
-from . import executor as X
 from . import ops
+from . import patchgan
 from . import plans as PL
 from . import torch_rng
-from ._lib import FG_ACT_LRELU, FG_ACT_NONE, FG_ACT_RELU, FG_PAD_ZERO, require_device
+from ._lib import FG_ACT_LRELU, FG_ACT_RELU, FG_PAD_ZERO, require_device
+from .layers import Grads, bn_stats_for, conv_fwd, convT_bwd, convT_fwd, decided, dgrad_s2, wgrad_conv
 from .plans import Buf, Slice
 
 N_LEVELS = 8
@@ -166,31 +168,12 @@ def draw_dropout_masks(n, h, w):
 # generator
 # ======================================================================================
 
-def _conv_nb(P, name, X_, pad, k, stride, Y, act=FG_ACT_NONE, tag=None):
-    """conv whose module may have no bias (bias=False in the reference)"""
-    w = P[name + ".weight"]
-    m = PL.wmap_conv_fwd(w.shape, X_.c)
-    ops.conv([PL.conv_problem(X_, pad, k, stride, ops.pack_weight(w, m), m, Y, bias=P.get(name + ".bias"), act=act)],
-             tag=tag)
+_conv_nb = conv_fwd          # (the name tests/test_gpu_unet_convs.py and tests/test_gpu_seg_train.py call it by)
 
 
 def _convT4(P, name, X_, Y):
-    """ConvTranspose2d(k=4, s=2, p=1) over X_ (zero border >= 1): four phase GEMMs"""
-    w = P[name + ".weight"]
-    maps = PL.phase_maps(w.shape, 4, 1, X_.c)
-    wps = [ops.pack_weight(w, m) for m, _, _ in maps]
-    ops.conv(PL.phase_problems(X_, w.shape, 4, 1, Y, wps, maps, bias=P.get(name + ".bias")))
-
-
-def _stats(B, name, src, groups, training):
-    """batch statistics (+ running-stat update) or, in eval mode, the running statistics"""
-    rm, rv = B[name + ".running_mean"], B[name + ".running_var"]
-    if training:
-        return ops.bn_stats(src, groups, (rm, rv, B.get(name + ".num_batches_tracked")))
-    mean, invstd = ops.bn_eval_stats(rm, rv)
-    if groups > 1:
-        mean, invstd = mean.repeat(groups), invstd.repeat(groups)
-    return mean, invstd
+    """an up conv: ConvTranspose2d(k=4, s=2, p=1) over X_ (zero border >= 1)"""
+    convT_fwd(P, name, X_, Y, 4, 1)
 
 
 def check_input_size(H, W):
@@ -220,7 +203,7 @@ def gen_forward(P, B, x, masks=None, training=True, save=True):
         inner = ch[k - 1][1]
         h, w = H >> k, W >> k
         c = Buf.empty(N, h, w, inner, 0, dev)
-        _conv_nb(P, nm["down"], a, 1, 4, 2, c)
+        conv_fwd(P, nm["down"], a, 1, 4, 2, c)
         L = dict(a=a, c=c)
         if k == N_LEVELS:
             r = Buf.zeros(N, h, w, inner, 1, dev)
@@ -229,7 +212,7 @@ def gen_forward(P, B, x, masks=None, training=True, save=True):
         else:
             mean = invstd = None
             if "downnorm" in nm:
-                mean, invstd = _stats(B, nm["downnorm"], c, 1, training)
+                mean, invstd = bn_stats_for(B, nm["downnorm"], c, 1, training)
             nxt = Buf.zeros(N, h, w, inner, 1, dev)
             cat = Buf.zeros(N, h, w, 2 * inner, 1, dev)
             slot = ops.amax_slot(cat)               # one operand-scale slot, raised by both halves' producers
@@ -248,7 +231,7 @@ def gen_forward(P, B, x, masks=None, training=True, save=True):
         h, w = H >> (k - 1), W >> (k - 1)
         u = Buf.empty(N, h, w, outer, 0, dev)
         _convT4(P, nm["up"], L["r"] if k == N_LEVELS else L["cat"], u)
-        mean, invstd = _stats(B, nm["upnorm"], u, 1, training)
+        mean, invstd = bn_stats_for(B, nm["upnorm"], u, 1, training)
         parent = S["lv"][k - 1]
         inner_p = ch[k - 2][1]
         ops.bn_apply(u, 1, mean, invstd, P[nm["upnorm"] + ".weight"], P[nm["upnorm"] + ".bias"], dmask.get(k),
@@ -269,22 +252,17 @@ def gen_backward(P, S, g_out, grads_into=None, ready=None, accumulate=False):
     ready = ready or (lambda name: None)
     N, H, W = S["N"], S["H"], S["W"]
     dev = g_out.device
-    G = X._Grads(P, grads_into, accumulate, device=dev)
+    G = Grads(P, grads_into, accumulate)
     ch = level_channels(S["x"].shape[1])
     lv = S["lv"]
     # ---- tanh head + outermost up conv (bias)
     nm = level_names(1)
     g_logits = Buf.empty(N, H, W, 4, 1, dev)
     ops.tanh_head_bwd(S["logits"], 3, g_out, g_logits)
-    w = P[nm["up"] + ".weight"]
-    G.wgrad(PL.wgrad_convT(lv[1]["cat"], g_logits, 4, 1, w.shape[0]), PL.wmap_wgrad(w.shape, True, g_logits.c, 4),
-            nm["up"] + ".weight", (lv[1]["cat"], g_logits))
-    ops.channel_sum(g_logits, 3, G.get(nm["up"] + ".bias"), G.acc)
-    G.ready(ready, nm["up"])
-    g_cat = {}
-    g_cat[1] = Buf.empty(N, H >> 1, W >> 1, w.shape[0], 0, dev)
-    m = PL.wmap_convT_dgrad(w.shape, g_logits.c)
-    ops.conv([PL.conv_problem(g_logits, 1, 4, 2, ops.pack_weight(w, m), m, g_cat[1])])
+    cat1 = lv[1]["cat"]
+    g_cat = {1: Buf.empty(N, cat1.h, cat1.w, cat1.c, 0, dev)}
+    convT_bwd(P, G, nm["up"], cat1, g_logits, 4, 1, g_cat[1], bias_channels=3)
+    ready(nm["up"])
     # ---- up chain: level k's upnorm + up conv, k = 2 .. 8
     g_c = None
     for k in range(2, N_LEVELS + 1):
@@ -298,13 +276,9 @@ def gen_backward(P, S, g_out, grads_into=None, ready=None, accumulate=False):
                    G.get(nm["upnorm"] + ".weight"), G.get(nm["upnorm"] + ".bias"), G.acc)
         ops.zero_border(g_u)
         xin = L["r"] if k == N_LEVELS else L["cat"]
-        w = P[nm["up"] + ".weight"]
-        G.wgrad(PL.wgrad_convT(xin, g_u, 4, 1, w.shape[0]), PL.wmap_wgrad(w.shape, True, g_u.c, 4),
-                nm["up"] + ".weight", (xin, g_u))
-        G.ready(ready, nm["up"])
         g_x = Buf.empty(N, xin.h, xin.w, xin.c, 0, dev)
-        m = PL.wmap_convT_dgrad(w.shape, g_u.c)
-        ops.conv([PL.conv_problem(g_u, 1, 4, 2, ops.pack_weight(w, m), m, g_x)])
+        convT_bwd(P, G, nm["up"], xin, g_u, 4, 1, g_x)
+        ready(nm["up"])
         if k == N_LEVELS:
             g_c = Buf.empty(N, xin.h, xin.w, xin.c, 1, dev)      # through ReLU(D_8)
             ops.bn_bwd(g_x, FG_ACT_RELU, None, 0, L["c"], 1, None, None, None, None, None, g_c)
@@ -323,18 +297,17 @@ def gen_backward(P, S, g_out, grads_into=None, ready=None, accumulate=False):
                        P[nm["downnorm"] + ".weight"], P[nm["downnorm"] + ".bias"], None, g_c,
                        G.get(nm["downnorm"] + ".weight"), G.get(nm["downnorm"] + ".bias"), G.acc)
             ops.zero_border(g_c)
-        X._wgrad_conv(P, G, nm["down"], g_c, L["a"], 1, 4, 2)
-        G.ready(ready, nm["down"])
+        wgrad_conv(P, G, nm["down"], g_c, L["a"], 1, 4, 2)
+        ready(nm["down"])
         a = L["a"]
         g_a = Buf.empty(N, a.h, a.w, a.c, 0, dev)
-        X._dgrad_s2(P, nm["down"], g_c, 4, Y=g_a)
+        dgrad_s2(P, nm["down"], g_c, 4, Y=g_a)
     L = lv[1]
     nm = level_names(1)
     g_d1 = Buf.empty(N, L["c"].h, L["c"].w, 64, 0, dev)
     ops.bn_bwd(g_a, FG_ACT_LRELU, Slice(g_cat[1], 0, 64), FG_ACT_RELU, L["c"], 1, None, None, None, None, None, g_d1)
-    X._wgrad_conv(P, G, nm["down"], g_d1, L["a"], 1, 4, 2)
-    G.ready(ready, nm["down"])
-    G.join()
+    wgrad_conv(P, G, nm["down"], g_d1, L["a"], 1, 4, 2)
+    ready(nm["down"])
     return G.out
 
 
@@ -343,12 +316,12 @@ def gen_act_decisions(S):
     (test instrumentation for teacher-forced gradient comparisons)"""
     lv = S["lv"]
     ch = level_channels(S["x"].shape[1])
-    out = {"inner": X._decided(lv[N_LEVELS]["r"])}
+    out = {"inner": decided(lv[N_LEVELS]["r"])}
     for k in range(1, N_LEVELS):
-        out[f"down{k}"] = X._decided(lv[k + 1]["a"])
+        out[f"down{k}"] = decided(lv[k + 1]["a"])
     for k in range(2, N_LEVELS + 1):
         inner_p = ch[k - 2][1]
-        out[f"up{k}"] = X._decided(Slice(lv[k - 1]["cat"], inner_p, inner_p))
+        out[f"up{k}"] = decided(Slice(lv[k - 1]["cat"], inner_p, inner_p))
     return out
 
 
@@ -356,90 +329,43 @@ def gen_act_decisions(S):
 # discriminator
 # ======================================================================================
 
+class DiscBatchNorm:
+    """patchgan's norm object: BatchNorm2d (model.3 / .6 / .9) + LeakyReLU over `groups` separate calls stacked along
+    the batch, B's running statistics updated in training mode; the convs under it have no bias"""
+
+    conv_stats = False
+
+    def __init__(self, B, groups, training):
+        self.B, self.groups, self.training = B, groups, training
+
+    def forward(self, P, conv, e, stats, fp32):
+        norm = DISC_NORMS[conv]
+        mean, invstd = bn_stats_for(self.B, norm, e, self.groups, self.training)
+        a = Buf.zeros(e.n, e.h, e.w, e.c, 1, e.t.device)
+        ops.bn_apply(e, self.groups, mean, invstd, P[norm + ".weight"], P[norm + ".bias"], None, FG_ACT_LRELU, a)
+        return dict(e=e, mean=mean, invstd=invstd, a=a)
+
+    def backward(self, P, G, conv, L, g_a, g_e):
+        norm = DISC_NORMS[conv]
+        gg, gb = (G.get(norm + ".weight"), G.get(norm + ".bias")) if G is not None else (None, None)
+        ops.bn_bwd(g_a, FG_ACT_LRELU, None, 0, L["e"], self.groups, L["mean"], L["invstd"], P[norm + ".weight"],
+                   P[norm + ".bias"], None, g_e, gg, gb)
+        ops.zero_border(g_e)
+
+
 def disc_forward(P, B, inp, groups=1, training=True, save=True):
     """inp: Buf from executor.disc_pack (zero border 1), groups: separate BatchNorm calls stacked
     along the batch.  Returns (pred [N, 1, ho, wo], saved)."""
-    N, H, W = inp.n, inp.h, inp.w
-    dev = inp.t.device
-    if H < 24 or W < 24:
-        raise RuntimeError(f"Pix2PixDiscriminator needs H, W >= 24 (got {H}x{W})")
-    h1, w1 = PL.out_size(H, 4, 2, 1), PL.out_size(W, 4, 2, 1)
-    e0 = Buf.empty(N, h1, w1, 64, 1, dev)
-    _conv_nb(P, "model.0", inp, 1, 4, 2, e0, act=FG_ACT_LRELU)
-    ops.zero_border(e0)
-    S = dict(inp=inp, e0=e0, groups=groups)
-    prev = e0
-    for conv, stride, c in (("model.2", 2, 128), ("model.5", 2, 256), ("model.8", 1, 512)):
-        norm = DISC_NORMS[conv]
-        hh, ww = PL.out_size(prev.h, 4, stride, 1), PL.out_size(prev.w, 4, stride, 1)
-        e = Buf.empty(N, hh, ww, c, 0, dev)
-        _conv_nb(P, conv, prev, 1, 4, stride, e, tag="p2p_d_model8_fwd" if conv == "model.8" else None)
-        mean, invstd = _stats(B, norm, e, groups, training)
-        a = Buf.zeros(N, hh, ww, c, 1, dev)
-        ops.bn_apply(e, groups, mean, invstd, P[norm + ".weight"], P[norm + ".bias"], None, FG_ACT_LRELU, a)
-        S[conv] = dict(x=prev, e=e, mean=mean, invstd=invstd, a=a)
-        prev = a
-    h5, w5 = PL.out_size(prev.h, 4, 1, 1), PL.out_size(prev.w, 4, 1, 1)
-    pred = torch.empty(N, 1, h5, w5, dtype=torch.float32, device=dev)
-    ops.conv_n1_fwd(prev, P["model.11.weight"], P["model.11.bias"], pred)
-    return pred, (S if save else None)
+    return patchgan.forward(P, inp, DiscBatchNorm(B, groups, training), save, "Pix2PixDiscriminator",
+                            tags={"model.8": "p2p_d_model8_fwd"})
 
 
 def disc_backward(P, S, g_pred, param_grads=True, grads_into=None, input_grad=None, input_grad_channels=None,
                   input_grad_accumulate=False, ready=None):
-    """Explicit backward of disc_forward (see executor.disc_backward for the arguments)."""
-    ready = (ready if param_grads and ready is not None else (lambda name: None))
-    inp, groups = S["inp"], S["groups"]
-    N = inp.n
-    dev = inp.t.device
-    G = X._Grads(P, grads_into, device=dev)
-    a3 = S["model.8"]["a"]
-    h5, w5 = g_pred.shape[2], g_pred.shape[3]
-    g11 = Buf.empty(N, h5, w5, 1, 3, dev)
-    ops.pack_input(g_pred, 1, None, 0, g11, 0, N, FG_PAD_ZERO)
-    if param_grads:
-        w11 = P["model.11.weight"]
-        G.off_path(lambda: ops.conv_n1_wgrad(a3, g11, PL.wmap_wgrad(w11.shape, True, a3.c, 4),
-                                             G.get("model.11.weight")), (a3, g11), ("model.11.weight",))
-        ops.channel_sum(g11, 1, G.get("model.11.bias"))
-        G.ready(ready, "model.11")
-    g_a = Buf.empty(N, a3.h, a3.w, 512, 0, dev)
-    X._dgrad_s1(P, "model.11", g11, 2, 4, g_a)
-    for conv, stride in (("model.8", 1), ("model.5", 2), ("model.2", 2)):
-        norm = DISC_NORMS[conv]
-        L = S[conv]
-        e = L["e"]
-        g_e = Buf.empty(N, e.h, e.w, e.c, 2 if stride == 1 else 1, dev)
-        ops.bn_bwd(g_a, FG_ACT_LRELU, None, 0, e, groups, L["mean"], L["invstd"], P[norm + ".weight"],
-                   P[norm + ".bias"], None, g_e, G.get(norm + ".weight") if param_grads else None,
-                   G.get(norm + ".bias") if param_grads else None)
-        ops.zero_border(g_e)
-        if param_grads:
-            X._wgrad_conv(P, G, conv, g_e, L["x"], 1, 4, stride)
-            G.ready(ready, conv)
-        xprev = L["x"]
-        g_a = Buf.empty(N, xprev.h, xprev.w, xprev.c, 1 if conv == "model.2" else 0, dev)
-        if stride == 1:
-            X._dgrad_s1(P, conv, g_e, 2, 4, g_a)
-        else:
-            X._dgrad_s2(P, conv, g_e, 4, Y=g_a)
-    e0 = S["e0"]
-    g_e0 = g_a
-    ops.zero_border(g_e0)
-    ops.act_bwd(g_e0, e0, FG_ACT_LRELU)
-    if param_grads:
-        X._wgrad_conv(P, G, "model.0", g_e0, inp, 1, 4, 2)
-        ops.channel_sum(g_e0, 64, G.get("model.0.bias"))
-        G.ready(ready, "model.0")
-    if input_grad is not None:
-        c0, cn = input_grad_channels
-        assert input_grad.is_contiguous() and input_grad.shape[1] >= cn
-        X._dgrad_s2(P, "model.0", g_e0, 4, y_nchw=(input_grad.view(-1), input_grad.shape[1], inp.h, inp.w),
-                    n_base=c0, n_out=cn, accumulate=int(input_grad_accumulate))
-    G.join()
-    return G.out
+    """Explicit backward of disc_forward (patchgan.backward documents the arguments).  The restricted input gradient
+    stays on the conv engine."""
+    return patchgan.backward(P, S, g_pred, param_grads, grads_into, input_grad, input_grad_channels,
+                             input_grad_accumulate, ready)
 
 
-def disc_act_decisions(S, lo=0, hi=None):
-    return {"model.0": X._decided(S["e0"], lo, hi), "model.2": X._decided(S["model.2"]["a"], lo, hi),
-            "model.5": X._decided(S["model.5"]["a"], lo, hi), "model.8": X._decided(S["model.8"]["a"], lo, hi)}
+disc_act_decisions = patchgan.act_decisions

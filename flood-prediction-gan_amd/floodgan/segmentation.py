@@ -1,5 +1,5 @@
 """The flood-segmentation U-Net the evaluation scores generator outputs with:
-drop-in modules and a native forward executor.
+drop-in modules and a native forward / backward executor on the layer kit (floodgan.layers).
 
 Reference: models/model_architectures.py:508-587 (UNet, DoubleConv, Down, Up, OutConv; milesial
 style, bilinear=False), models/segmentation_model.py:19-72 (SegmentationModel: construction,
@@ -31,11 +31,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import executor as X
 from . import ops
-from . import pix2pix as P2P
 from . import plans as PL
 from ._lib import FG_ACT_RELU, FG_PAD_ZERO, require_device
+from .layers import Grads, bn_stats_for, conv_fwd, convT_bwd, convT_fwd, decided, dgrad_s1, wgrad_conv
 from .plans import Buf, Slice
 
 ENC = [64, 128, 256, 512, 1024]
@@ -61,11 +60,11 @@ def check_input_size(H, W):
 
 
 def _stats(B, name, src, training, update_running):
-    """P2P._stats, or -- a frozen network evaluated as the reference evaluates it -- the batch statistics with the
-    running statistics and num_batches_tracked left alone"""
+    """layers.bn_stats_for, or -- a frozen network evaluated as the reference evaluates it -- the batch statistics
+    with the running statistics and num_batches_tracked left alone"""
     if training and not update_running:
         return ops.bn_stats(src, 1, None)
-    return P2P._stats(B, name, src, 1, training)
+    return bn_stats_for(B, name, src, 1, training)
 
 
 def _double_conv(P, B, names, X, mid, out, training, dsts, save=None, operands=True, update_running=True):
@@ -76,12 +75,12 @@ def _double_conv(P, B, names, X, mid, out, training, dsts, save=None, operands=T
     N, h, w = X.n, X.h, X.w
     dev = X.t.device
     t = Buf.empty(N, h, w, mid, 0, dev)
-    P2P._conv_nb(P, c1, X, 1, 3, 1, t)
+    conv_fwd(P, c1, X, 1, 3, 1, t)
     mean, invstd = _stats(B, b1, t, training, update_running)
     a = Buf.zeros(N, h, w, mid, 1, dev)
     ops.bn_apply(t, 1, mean, invstd, P[b1 + ".weight"], P[b1 + ".bias"], None, FG_ACT_RELU, a)
     u = Buf.empty(N, h, w, out, 0, dev)
-    P2P._conv_nb(P, c2, a, 1, 3, 1, u)
+    conv_fwd(P, c2, a, 1, 3, 1, u)
     mean2, invstd2 = _stats(B, b2, u, training, update_running)
     ops.bn_apply(u, 1, mean2, invstd2, P[b2 + ".weight"], P[b2 + ".bias"], None, FG_ACT_RELU, dsts[0],
                  FG_ACT_RELU if dsts[1] is not None else 0, dsts[1])
@@ -93,10 +92,7 @@ def _double_conv(P, B, names, X, mid, out, training, dsts, save=None, operands=T
 
 def _convT2(P, name, X, Y):
     """ConvTranspose2d(k=2, s=2) over X (border >= 1) into Y (Buf or Slice): four single-tap phases"""
-    w = P[name + ".weight"]
-    maps = PL.phase_maps(w.shape, 2, 0, X.c)
-    wps = [ops.pack_weight(w, m) for m, _, _ in maps]
-    ops.conv(PL.phase_problems(X, w.shape, 2, 0, Y, wps, maps, bias=P.get(name + ".bias")))
+    convT_fwd(P, name, X, Y, 2, 0)
 
 
 def unet_logits(P, B, X0, training=True, save=False, update_running=True):
@@ -143,7 +139,7 @@ def unet_logits(P, B, X0, training=True, save=False, update_running=True):
             S["dec"][i].update(xin=X, out=y)                       # the ConvTranspose input, the level output
         X = y
     logits = Buf.empty(N, H, W, 4, 0, dev)
-    P2P._conv_nb(P, head, X, 0, 1, 1, logits)
+    conv_fwd(P, head, X, 0, 1, 1, logits)
     return (logits, S) if save else logits
 
 
@@ -174,14 +170,14 @@ def _double_conv_bwd(P, G, names, D, gA, gB=None, need_input=True, split=None, f
     _bn_bwd(G, P, b2, gA, gB, u, D["m2"], D["i2"], g_u, fixed, param_grads)
     ops.zero_border(g_u)
     if param_grads:
-        X._wgrad_conv(P, G, c2, g_u, D["a"], 1, 3, 1)
+        wgrad_conv(P, G, c2, g_u, D["a"], 1, 3, 1)
     g_a = Buf.empty(N, h, w, t.c, 0, dev)
-    X._dgrad_s1(P, c2, g_u, 1, 3, g_a)
+    dgrad_s1(P, c2, g_u, 1, 3, g_a)
     g_t = Buf.empty(N, h, w, t.c, 1, dev)
     _bn_bwd(G, P, b1, g_a, None, t, D["m1"], D["i1"], g_t, fixed, param_grads)
     ops.zero_border(g_t)
     if param_grads:
-        X._wgrad_conv(P, G, c1, g_t, D["x"], 1, 3, 1)
+        wgrad_conv(P, G, c1, g_t, D["x"], 1, 3, 1)
     if not need_input:
         return None
     wt = P[c1 + ".weight"]
@@ -189,7 +185,7 @@ def _double_conv_bwd(P, G, names, D, gA, gB=None, need_input=True, split=None, f
     if split is None:
         # (inc: 3 image channels in a 4-channel buffer, the engine writing 3 -- as the head writes 1 of 4)
         g_x = Buf.empty(N, h, w, c_in, 0, dev) if c_in % 4 == 0 else Buf.zeros(N, h, w, PL.rup(c_in, 4), 0, dev)
-        X._dgrad_s1(P, c1, g_t, 1, 3, g_x)
+        dgrad_s1(P, c1, g_t, 1, 3, g_x)
         return g_x
     assert c_in == 2 * split
     halves, probs = [], []
@@ -203,17 +199,12 @@ def _double_conv_bwd(P, G, names, D, gA, gB=None, need_input=True, split=None, f
 
 
 def _convT2_bwd(P, G, name, xin, g_y, param_grads=True):
-    """Backward of _convT2 (ConvTranspose2d(k=2, s=2, p=0), weight (I, O, 2, 2)): g_y [N, 2h, 2w, O] (no border
-    needed: the four taps tile the output) -> the gradient of xin [N, h, w, I]; weight and bias gradients into G
-    (param_grads=False: neither, and xin is not read)"""
+    """Backward of a decoder level's ConvTranspose2d(k=2, s=2, p=0), weight (I, O, 2, 2): g_y [N, 2h, 2w, O] (no
+    border needed: the four taps tile the output) -> the gradient of xin [N, h, w, I]; weight and bias gradients
+    into G (param_grads=False: neither, and xin is not read)"""
     wt = P[name + ".weight"]
-    if param_grads:
-        G.wgrad(PL.wgrad_convT(xin, g_y, 2, 0, wt.shape[0]), PL.wmap_wgrad(wt.shape, True, g_y.c, 2),
-                name + ".weight", (xin, g_y))
-        ops.channel_sum(g_y, wt.shape[1], G.get(name + ".bias"), G.acc)
     g_x = Buf.empty(g_y.n, g_y.h // 2, g_y.w // 2, wt.shape[0], 0, g_y.t.device)
-    m = PL.wmap_convT_dgrad(wt.shape, g_y.c)
-    ops.conv([PL.conv_problem(g_y, 0, 2, 2, ops.pack_weight(wt, m), m, g_x)])     # one GEMM, K = 4 O
+    convT_bwd(P, G, name, xin, g_y, 2, 0, g_x, param_grads=param_grads, bias_channels=wt.shape[1])   # K = 4 O
     return g_x
 
 
@@ -240,7 +231,7 @@ def unet_backward(P, S, g_logits, grads_into=None, choices=None, *, input_grad=F
         raise RuntimeError(f"unet_backward: logits gradient {g_logits.n}x{g_logits.h}x{g_logits.w} for a saved "
                            f"forward of {N}x{H}x{W}")
     dev = g_logits.t.device
-    G = X._Grads(P, grads_into, device=dev)
+    G = Grads(P, grads_into)
     enc, dec, head = layer_names()
     # ---- OutConv 1x1, 64 -> 1 (weight + bias, then the input gradient)
     if param_grads:
@@ -272,7 +263,6 @@ def unet_backward(P, S, g_logits, grads_into=None, choices=None, *, input_grad=F
             gB = g_skip.pop(k)
         g = _double_conv_bwd(P, G, enc[k], E, gA, gB, need_input=k > 0 or input_grad, fixed=fixed,
                              param_grads=param_grads)
-    G.join()
     if input_grad:
         G.out["input"] = g
     return G.out
@@ -285,9 +275,14 @@ def unet_decisions(S):
     enc, dec, _ = layer_names()
     out = {}
     for names, D in list(zip(enc, S["enc"])) + [(n, D) for (_, n), D in zip(dec, S["dec"])]:
-        out[names[1]] = X._decided(D["a"])
-        out[names[3]] = X._decided(D["out"])
+        out[names[1]] = decided(D["a"])
+        out[names[3]] = decided(D["out"])
     return out
+
+
+def _nchw(buf, c):
+    """channels 0 .. c of a Buf's interior as an [N, c, H, W] view"""
+    return buf.interior()[..., :c].permute(0, 3, 1, 2)
 
 
 def unit_image(x, buf=None, nchw=True):
@@ -336,7 +331,7 @@ class _UNetFn(torch.autograd.Function):
             ctx.save_for_backward(*params)
         else:
             logits = unet_logits(P, B, X0, module.training)
-        return logits.interior()[..., :1].permute(0, 3, 1, 2).contiguous()
+        return _nchw(logits, 1).contiguous()
 
     @staticmethod
     def backward(ctx, g):
@@ -350,7 +345,7 @@ class _UNetFn(torch.autograd.Function):
         g_logits = Buf.empty(S["N"], S["H"], S["W"], 4, 0, g.device)
         ops.pack_input(g, 1, None, 0, g_logits, 0, S["N"], FG_PAD_ZERO)
         grads = unet_backward(P, S, g_logits, input_grad=wants_x, param_grads=wants_p)
-        g_x = grads["input"].interior()[..., :3].permute(0, 3, 1, 2).contiguous() if wants_x else None
+        g_x = _nchw(grads["input"], 3).contiguous() if wants_x else None
         return (None, None, g_x) + tuple(grads[k] if need and wants_p else None
                                          for k, need in zip(P, ctx.needs_input_grad[3:]))
 
@@ -505,7 +500,7 @@ class SegStep:
         choices = {} if self.record_decisions else None
         if self.record_decisions:
             self.decisions = dict(relu=unet_decisions(S), pool=choices,
-                                  logits=logits.interior()[..., :1].permute(0, 3, 1, 2).cpu())
+                                  logits=_nchw(logits, 1).cpu())
         unet_backward(self.P, S, g, grads_into={k: p.grad for k, p in self.P.items()}, choices=choices)
         del S
         if choices:
@@ -641,7 +636,7 @@ class FloodMaskLoss(nn.Module):
         with torch.no_grad():
             P, B = self._state()
             _, _, _, z, r = _flood_mask_pass(P, B, fake, real, self.batch_stats, False)
-        return tuple(b.interior()[..., :1].permute(0, 3, 1, 2).contiguous() for b in (z, r))
+        return tuple(_nchw(b, 1).contiguous() for b in (z, r))
 
     def fused_term(self, weight):
         """this loss as the fake_loss hook of the fused paired step (PairedStep / Pix2PixStep)"""
@@ -704,6 +699,16 @@ class SegmentationModel:
         from .data import create_masks_dataset
         return create_masks_dataset(self.dataset_subset, self.data_path, self.train_on_all, csv_path=self.csv_path,
                                     staged=self.staged_loader, device=self.device)
+
+    def _eval_loader(self, use_test_data):
+        """the validation (or test) loader: the assigned one, else built from data_path"""
+        val_loader, test_loader = self.val_loader, self.test_loader
+        if val_loader is None and test_loader is None and self.data_path is not None:
+            _, val_loader, test_loader = self._loaders()
+        loader = test_loader if use_test_data else val_loader
+        if loader is None:
+            raise RuntimeError("no evaluation data: pass data_path or assign val_loader / test_loader")
+        return loader
 
     def lambda_rule(self, epoch):
         """models/segmentation_model.py:86-92: constant for the first half of the epochs, then linear decay"""
@@ -782,12 +787,7 @@ class SegmentationModel:
         import pandas as pd
 
         from .evaluate import MaskConfusion
-        val_loader, test_loader = self.val_loader, self.test_loader
-        if val_loader is None and test_loader is None and self.data_path is not None:
-            _, val_loader, test_loader = self._loaders()
-        loader = test_loader if use_test_data else val_loader
-        if loader is None:
-            raise RuntimeError("no evaluation data: pass data_path or assign val_loader / test_loader")
+        loader = self._eval_loader(use_test_data)
         conf = MaskConfusion(self.device)
         for input_image, true_mask, _ in loader:
             x = input_image.to(self.device)
@@ -843,12 +843,7 @@ class SegmentationModel:
         import os
 
         from .render import save_sheet
-        val_loader, test_loader = self.val_loader, self.test_loader
-        if val_loader is None and test_loader is None and self.data_path is not None:
-            _, val_loader, test_loader = self._loaders()
-        loader = test_loader if use_test_data else val_loader
-        if loader is None:
-            raise RuntimeError("no evaluation data: pass data_path or assign val_loader / test_loader")
+        loader = self._eval_loader(use_test_data)
         xs, ts, ps, names = [], [], [], []
         torch.manual_seed(self.seed)
         for i, (input_image, true_mask, image_name) in enumerate(loader):

@@ -56,7 +56,7 @@ def win_fwd(dev):
 def deconv2(kind, dev):
     """deconv2 (ConvTranspose2d(128, 64, 3, 2, 1, 1), bs 8, 256^2 -> 512^2) on a pre-split relu(IN(.)) operand with
     the statistics epilogue: quad_stats = the quad form, convT4_stats = the four phase problems"""
-    from floodgan import executor as X
+    from floodgan import layers
     L.set_conv_math("f16x3")
     N, H = 8, 256
     c = Buf.empty(N, H, H, 128, 0, dev)
@@ -67,7 +67,7 @@ def deconv2(kind, dev):
     P = {"t.weight": torch.randn(128, 64, 3, 3, device=dev) * 0.05, "t.bias": torch.zeros(64, device=dev)}
     Y = Buf.empty(N, 2 * H, 2 * H, 64, 0, dev)
     if kind == "quad_stats":
-        return lambda: X._convT_fwd(P, "t", S, Y)
+        return lambda: layers.convT_fwd(P, "t", S, Y, 3, 1, in_stats=True)
     from floodgan import plans as PL
     maps = PL.phase_maps(P["t.weight"].shape, 3, 1, S.c)
     wps = [ops.pack_weight(P["t.weight"], m) for m, _, _ in maps]

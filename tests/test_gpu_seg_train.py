@@ -286,7 +286,7 @@ def test_head_forward_one_output_in_four_channels(conv_math, report):
 @pytest.mark.parametrize("shape", [(2, 128, 6, 10), (1, 1024, 2, 2)])
 def test_convT2_backward_vs_fp64(shape):
     """ConvTranspose2d(k=2, s=2, p=0) backward alone at the narrowest and the widest level"""
-    from floodgan import executor as X
+    from floodgan import layers
     from floodgan import segmentation as S
     N, Cin, H, W = shape
     g = torch.Generator().manual_seed(Cin)
@@ -295,7 +295,7 @@ def test_convT2_backward_vs_fp64(shape):
     b = torch.randn((Cin // 2,), generator=g)
     gy = torch.randn((N, Cin // 2, 2 * H, 2 * W), generator=g)
     P = {"up.weight": w.to(DEV), "up.bias": b.to(DEV)}
-    G = X._Grads(P, device=DEV)
+    G = layers.Grads(P)
     g_x = S._convT2_bwd(P, G, "up", buf_from(x, 1, "constant"), buf_from(gy, 0, "constant"))
     rx, rw, rb = SO.convT2_grads(x.double(), w.double(), b.double(), gy.double())
     e = dict(input=nrel(nchw(g_x), rx), weight=nrel(G.out["up.weight"], rw), bias=nrel(G.out["up.bias"], rb))

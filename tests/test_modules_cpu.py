@@ -126,6 +126,45 @@ def test_c_abi_library_exports_every_declared_symbol():
     assert lib.fg_in_workspace_doubles(8, 256) > 0
 
 
+def test_no_module_reaches_into_a_siblings_private_names():
+    """No module of the package reads an underscore-prefixed (non-dunder) name of a sibling module, neither as an
+    attribute of the imported module nor by `from .sibling import _name`: what several modules share is public
+    (floodgan.layers).  `_lib` is the binding module's own name, not a private name of another module."""
+    import ast
+    import importlib
+    import pkgutil
+
+    import floodgan
+    siblings = {m.name for m in pkgutil.iter_modules(floodgan.__path__)}
+    assert {"executor", "pix2pix", "segmentation", "model", "ops"} <= siblings, siblings
+
+    def private(name):
+        return name.startswith("_") and not (name.startswith("__") and name.endswith("__"))
+
+    found = []
+    for mod in sorted(siblings):
+        m = importlib.import_module("floodgan." + mod)
+        tree = ast.parse(open(m.__file__).read())
+        alias = {}                          # local name -> sibling module it is bound to
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and (node.level == 1 or (node.module or "").startswith("floodgan")):
+                src = (node.module or "").replace("floodgan", "").strip(".")
+                for a in node.names:
+                    if not src and a.name in siblings:          # from . import executor as X
+                        alias[a.asname or a.name] = a.name
+                    elif src in siblings and src != mod and private(a.name):   # from .executor import _Grads
+                        found.append(f"{mod}: from .{src} import {a.name}")
+            elif isinstance(node, ast.Import):
+                for a in node.names:
+                    if a.name.startswith("floodgan.") and a.asname:
+                        alias[a.asname] = a.name.split(".", 1)[1]
+        for node in ast.walk(tree):
+            if (isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in alias
+                    and alias[node.value.id] != mod and private(node.attr) and node.attr != "_lib"):
+                found.append(f"{mod}:{node.lineno}: {alias[node.value.id]}.{node.attr}")
+    assert not found, "\n".join(found)
+
+
 def test_two_n_batched_d_step_equals_reference_two_calls():
     """The fused step evaluates D(fake) and D(real) as ONE 2N batch (InstanceNorm is per
     sample): loss and gradients equal the reference's two calls (models/model.py:624-632)."""
