@@ -13,31 +13,13 @@
 // per thread, fp64 across threads / chunks / images.  Backward: the standard batch-norm adjoint over the
 // group, dL/dx = gamma * invstd * (g - mean(g) - xhat * mean(g xhat)), with g assembled from up to two
 // incoming gradients through their activations and the dropout mask.
-#include "fg_common.hpp"
+#include "amax_slot.hpp"
 
 namespace {
 
 constexpr int NT = 256;
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
-__device__ __forceinline__ void absmax_flush(unsigned m, unsigned* out) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
-    __shared__ unsigned red[NT / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned r = red[0];
-        for (int i = 1; i < NT / 64; ++i) r = max(r, red[i]);
-        atomicMax(out + (blockIdx.x & (FG_AMAX_SHARDS - 1)), r);
-    }
-    __syncthreads();    // red[] is free again: bn_apply_kernel flushes two slots in a row
-}
-__device__ __forceinline__ unsigned absbits4(const f32x4& v) {
-    return max(max(__float_as_uint(v[0]) & 0x7fffffffu, __float_as_uint(v[1]) & 0x7fffffffu),
-               max(__float_as_uint(v[2]) & 0x7fffffffu, __float_as_uint(v[3]) & 0x7fffffffu));
-}
 
 // Reductions are two-level and deterministic: the statistics kernels write one partial per (group,
 // chunk of pixels) -- each block walks its chunk over every image of its group -- and the finalize
@@ -194,8 +176,8 @@ __device__ __forceinline__ float act_apply(float v, int act) { return fg::act_fw
 // dst0 = act0(y), dst1 = act1(y) (interiors; the caller zeroes the borders)
 __global__ void bn_apply_kernel(fg_view src, int per_group, const float* __restrict__ mean,
                                 const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                const float* __restrict__ beta, const Drop drop, int act0, fg_view d0, unsigned* am0,
-                                int act1, fg_view d1, unsigned* am1) {
+                                const float* __restrict__ beta, const Drop drop, int act0, fg_view d0, float* am0,
+                                int act1, fg_view d1, float* am1) {
     const int C = src.c_alloc, C4 = C / 4;
     const long long total = (long long)src.n * src.h * src.w * C4;
     unsigned m0 = 0, m1 = 0;
@@ -221,17 +203,17 @@ __global__ void bn_apply_kernel(fg_view src, int per_group, const float* __restr
 #pragma unroll
         for (int e = 0; e < 4; ++e) o0[e] = act_apply(v[e], act0);
         *reinterpret_cast<f32x4*>(d0.ptr + fg::vidx(d0, n, y, x) + 4 * c4) = o0;
-        m0 = max(m0, absbits4(o0));
+        m0 = max(m0, fg::abs_bits(o0));
         if (d1.ptr) {
             f32x4 o1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o1[e] = act_apply(v[e], act1);
             *reinterpret_cast<f32x4*>(d1.ptr + fg::vidx(d1, n, y, x) + 4 * c4) = o1;
-            m1 = max(m1, absbits4(o1));
+            m1 = max(m1, fg::abs_bits(o1));
         }
     }
-    if (am0) absmax_flush(m0, am0);
-    if (am1) absmax_flush(m1, am1);
+    if (am0) fg::raise_block_max<NT>(am0, m0);
+    if (am1) fg::raise_block_max<NT>(am1, m1);
 }
 
 // the incoming gradient of the normalised (and dropped-out) value: gA * actA'(u) + gB * actB'(u), then
@@ -335,7 +317,7 @@ __global__ void bn_bwd_finalize_kernel(int N, int C, int groups, int HW, int chu
     if (gamma_grad) gamma_grad[c] = accumulate ? gamma_grad[c] + (float)tgx : (float)tgx;
 }
 
-__global__ void bn_bwd_apply_kernel(const BwdIn I, const float* __restrict__ coef, fg_view dst, unsigned* am) {
+__global__ void bn_bwd_apply_kernel(const BwdIn I, const float* __restrict__ coef, fg_view dst, float* am) {
     const int C = I.src.c_alloc, C4 = C / 4;
     const long long total = (long long)I.src.n * I.src.h * I.src.w * C4;
     unsigned m = 0;
@@ -359,15 +341,15 @@ __global__ void bn_bwd_apply_kernel(const BwdIn I, const float* __restrict__ coe
                 o[e] = gam[e] * is[e] * (gy[e] - coef[(size_t)(gc + e) * 2] - xh[e] * coef[(size_t)(gc + e) * 2 + 1]);
         }
         *reinterpret_cast<f32x4*>(dst.ptr + fg::vidx(dst, n, y, x) + 4 * c4) = o;
-        m = max(m, absbits4(o));
+        m = max(m, fg::abs_bits(o));
     }
-    if (am) absmax_flush(m, am);
+    if (am) fg::raise_block_max<NT>(am, m);
 }
 
 // The backward through FIXED per-channel statistics (module.eval(): mean / invstd do not depend on x, so the adjoint
 // has no mean terms): dst = gy * gamma * invstd, one streaming pass that reads src and the gradient(s) once and
 // writes dst once (16-byte accesses; src is read for the activation gates only)
-__global__ void bn_bwd_fixed_apply_kernel(const BwdIn I, fg_view dst, unsigned* am) {
+__global__ void bn_bwd_fixed_apply_kernel(const BwdIn I, fg_view dst, float* am) {
     const int C = I.src.c_alloc, C4 = C / 4;
     const long long total = (long long)I.src.n * I.src.h * I.src.w * C4;
     unsigned m = 0;
@@ -385,9 +367,9 @@ __global__ void bn_bwd_fixed_apply_kernel(const BwdIn I, fg_view dst, unsigned* 
         if (I.gamma) o = o * ld4(I.gamma + 4 * c4);
         o = o * ld4(I.invstd + 4 * c4);
         *reinterpret_cast<f32x4*>(dst.ptr + fg::vidx(dst, n, y, x) + 4 * c4) = o;
-        m = max(m, absbits4(o));
+        m = max(m, fg::abs_bits(o));
     }
-    if (am) absmax_flush(m, am);
+    if (am) fg::raise_block_max<NT>(am, m);
 }
 
 // 2x2 / stride-2 max pool (nn.MaxPool2d(2), models/model_architectures.py:558-560): floor sizes
@@ -480,7 +462,7 @@ FG_API int fg_bn_apply(fg_view src, int groups, const float* mean, const float* 
     const long long total = (long long)src.n * src.h * src.w * (src.c_alloc / 4);
     hipLaunchKernelGGL(bn_apply_kernel, dim3(fg::blocks_for(total, NT, 4096)), dim3(NT), 0, stream, src,
                        src.n / groups, mean, invstd, gamma, beta, make_drop(drop_mask, drop_scale, drop_seed), act0,
-                       dst0, reinterpret_cast<unsigned*>(absmax0), act1, dst1, reinterpret_cast<unsigned*>(absmax1));
+                       dst0, absmax0, act1, dst1, absmax1);
     return fg::launched("bn_apply");
 }
 
@@ -515,7 +497,7 @@ FG_API int fg_bn_bwd(fg_view gA, int actA, fg_view gB, int actB, fg_view src, in
     }
     const long long total = (long long)src.n * src.h * src.w * (C / 4);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(fg::blocks_for(total, NT, 4096)), dim3(NT), 0, stream, I, coef, dst,
-                       reinterpret_cast<unsigned*>(absmax));
+                       absmax);
     return fg::launched("bn_bwd_apply");
 }
 
@@ -549,7 +531,7 @@ FG_API int fg_bn_bwd_fixed(fg_view gA, int actA, fg_view gB, int actB, fg_view s
     }
     const long long total = (long long)src.n * src.h * src.w * (C / 4);
     hipLaunchKernelGGL(bn_bwd_fixed_apply_kernel, dim3(fg::blocks_for(total, NT, 4096)), dim3(NT), 0, stream, I, dst,
-                       reinterpret_cast<unsigned*>(absmax));
+                       absmax);
     return fg::launched("bn_bwd_fixed_apply");
 }
 

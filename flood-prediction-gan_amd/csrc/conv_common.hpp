@@ -1,7 +1,7 @@
 // Shared pieces of the convolution engine (conv_gemm.hip: generic register-staged kernels;
 // conv_f3.hip: the LDS-DMA pipelined f16x3 forward kernel).
 #pragma once
-#include "fg_common.hpp"
+#include "amax_slot.hpp"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -46,30 +46,8 @@ __device__ __forceinline__ void decomp(int m, int mb, int mab, int& img, int& a,
     }
 }
 
-// the power-of-two scale s = 2^(14-e) of a bound m < 2^e (1 for 0 / non-finite): |v * s| < 2^14
-__device__ __forceinline__ float pow2_of(float m) {
-    if (!(m > 0.f) || !(m < 3.0e38f)) return 1.f;
-    int e;
-    frexpf(m, &e);                                        // m < 2^e
-    return ldexpf(1.f, 14 - e);
-}
-
-// max over an absmax slot's FG_AMAX_SHARDS shards (every lane of the wave gets it)
-__device__ __forceinline__ float pow2_scale_max(const float* amax) {
-    unsigned b = __float_as_uint(amax[threadIdx.x & (FG_AMAX_SHARDS - 1)]) & 0x7fffffffu;
-#pragma unroll
-    for (int off = 1; off < FG_AMAX_SHARDS; off <<= 1) b = max(b, (unsigned)__shfl_xor((int)b, off));
-    return __uint_as_float(b);
-}
-
-// power-of-two operand scale from an absmax slot (max over its FG_AMAX_SHARDS shards, one per
-// lane, reduced across the wave): |v * s| < 2^14
-__device__ __forceinline__ float pow2_scale(const float* amax) {
-    unsigned b = amax ? __float_as_uint(amax[threadIdx.x & (FG_AMAX_SHARDS - 1)]) & 0x7fffffffu : 0u;
-#pragma unroll
-    for (int off = 1; off < FG_AMAX_SHARDS; off <<= 1) b = max(b, (unsigned)__shfl_xor((int)b, off));
-    return pow2_of(__uint_as_float(b));
-}
+// the operand scales come from the absmax slots (amax_slot.hpp)
+using fg::pow2_scale;
 
 // f16x3 split of 8 fp32 values: v*s = h + l, h = fp16(v*s), l = fp16(v*s - h)
 __device__ __forceinline__ void split_f16(const float (&v)[8], float s, f16x8& h, f16x8& l) {

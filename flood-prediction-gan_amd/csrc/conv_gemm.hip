@@ -1188,27 +1188,19 @@ __global__ void pack_weight_f16_batch_kernel(const PackBatch b) {
     }
 }
 
-// max |x| as the bit pattern of a non-negative float (uint order = float order; NaN sorts high)
-__global__ void absmax_kernel(const float* __restrict__ x, long long n, unsigned* __restrict__ out) {
+// max |x| of a flat array into its absmax slot
+__global__ void absmax_kernel(const float* __restrict__ x, long long n, float* __restrict__ out) {
     unsigned m = 0;
     const long long n4 = (((uintptr_t)x & 15) == 0) ? n / 4 : 0;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) m = max(m, __float_as_uint(v[e]) & 0x7fffffffu);
+        for (int e = 0; e < 4; ++e) m = max(m, fg::abs_bits(v[e]));
     }
     for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x)
-        m = max(m, __float_as_uint(x[i]) & 0x7fffffffu);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
-    __shared__ unsigned red[16];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = max(m, red[i]);
-        atomicMax(out + (blockIdx.x & (FG_AMAX_SHARDS - 1)), m);
-    }
+        m = max(m, fg::abs_bits(x[i]));
+    fg::raise_block_max(out, m);      // (the block size is the launch's: blockDim.x)
 }
 
 template <class SM, int BM, int BN, int WM, int WN, int MINW, int PF, bool SWZ = false>
@@ -1578,8 +1570,7 @@ FG_API int fg_pack_weight_f16_batch(const fg_pack_job* jobs, int njobs, hipStrea
 FG_API int fg_absmax(const float* x, long long n, float* out, hipStream_t stream) {
     if (!x || !out || n < 0) return fg::fail(FG_ERR_INVALID, "fg_absmax: bad args");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(absmax_kernel, dim3(fg::blocks_for((n + 3) / 4, 256, 2048)), dim3(256), 0, stream, x, n,
-                       reinterpret_cast<unsigned*>(out));
+    hipLaunchKernelGGL(absmax_kernel, dim3(fg::blocks_for((n + 3) / 4, 256, 2048)), dim3(256), 0, stream, x, n, out);
     return fg::launched("absmax");
 }
 

@@ -11,22 +11,6 @@
 
 namespace {
 
-// fold this thread's max |v| (as uint bits) into the absmax slot: block max, then one atomic
-// per block into shard blockIdx % FG_AMAX_SHARDS (256-thread blocks)
-__device__ __forceinline__ void absmax_flush(unsigned m, unsigned* out) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
-    __shared__ unsigned red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        atomicMax(out + (blockIdx.x & (FG_AMAX_SHARDS - 1)), max(max(red[0], red[1]), max(red[2], red[3])));
-}
-__device__ __forceinline__ unsigned absbits4(const f32x4& v) {
-    return max(max(__float_as_uint(v[0]) & 0x7fffffffu, __float_as_uint(v[1]) & 0x7fffffffu),
-               max(__float_as_uint(v[2]) & 0x7fffffffu, __float_as_uint(v[3]) & 0x7fffffffu));
-}
-
 constexpr int NT = 256;
 constexpr int MAX_CHUNKS = 256;
 constexpr int CS_CHUNKS = 1024;     // channel-sum blocks (workspace: fg_channel_sum_workspace_doubles)
@@ -151,7 +135,7 @@ __global__ void __launch_bounds__(64 * FG) in_finalize_kernel(fg_view src, int c
 }
 
 __global__ void in_apply_kernel(fg_view src, const float* __restrict__ mean, const float* __restrict__ rstd,
-                                int act, fg_view res, fg_view dst, int pad_mode, unsigned* __restrict__ amax) {
+                                int act, fg_view res, fg_view dst, int pad_mode, float* __restrict__ amax) {
     unsigned am = 0;
     const int C = dst.c_alloc, C4 = C / 4;
     const int hp = dst.h + 2 * dst.pad, wp = dst.w + 2 * dst.pad;
@@ -177,10 +161,10 @@ __global__ void in_apply_kernel(fg_view src, const float* __restrict__ mean, con
             for (int e = 0; e < 4; ++e) v[e] = fg::act_fwd(v[e], act);
             if (res.ptr) v += ld4(res.ptr + fg::vidx(res, n, y, x) + 4 * c4);
         }
-        am = max(am, absbits4(v));
+        am = max(am, fg::abs_bits(v));
         *reinterpret_cast<f32x4*>(dst.ptr + ((size_t)(n * hp + yp) * wp + xp) * C + 4 * c4) = v;
     }
-    if (amax) absmax_flush(am, amax);
+    if (amax) fg::raise_block_max<NT>(amax, am);
 }
 
 // FG_PRESPLIT store (include/floodgan.h) of this lane's 4 channels o (scaled by s) at p = its fp32 position:
@@ -315,7 +299,7 @@ template <bool NTL, bool HEAD = false>
 __global__ void __launch_bounds__(NT) in_apply_rows_kernel(fg_view src, const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, int act, fg_view res,
                                                            fg_view dst, int pad_mode, int lshift,
-                                                           unsigned* __restrict__ amax, float* __restrict__ split_slot,
+                                                           float* __restrict__ amax, float* __restrict__ split_slot,
                                                            float* __restrict__ ps_ptr, float* __restrict__ ps_slot,
                                                            const float* __restrict__ res_amax, int splitpix,
                                                            HeadArgs hd = HeadArgs{}) {
@@ -333,17 +317,17 @@ __global__ void __launch_bounds__(NT) in_apply_rows_kernel(fg_view src, const fl
     float ss = 0.f;
     if (split_slot) {
         const float bound = sqrtf((float)(h * w - 1)) * 1.001f;
-        ss = fgc::pow2_of(bound);
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(split_slot), __float_as_uint(bound));
+        ss = fg::pow2_of(bound);
+        if (blockIdx.x == 0 && threadIdx.x == 0) fg::raise_bound(split_slot, bound);
     }
     // dual output (ps_ptr): dst in fp32 AND a pre-split copy at the scale of |act(xhat) + res| <= sqrt(HW - 1) +
     // max|res| (the residual's absmax slot, reduced over its shards by every block alike)
     float* psrow = nullptr;
     if (ps_ptr) {
-        const float rmax = res_amax ? fgc::pow2_scale_max(res_amax) : 0.f;
+        const float rmax = res_amax ? fg::pow2_scale_max(res_amax) : 0.f;
         const float bound = (sqrtf((float)(h * w - 1)) + rmax) * 1.001f;
-        ss = fgc::pow2_of(bound);
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(ps_slot), __float_as_uint(bound));
+        ss = fg::pow2_of(bound);
+        if (blockIdx.x == 0 && threadIdx.x == 0) fg::raise_bound(ps_slot, bound);
         psrow = ps_ptr + (size_t)(n * hp + yp) * wp * C + 4 * c4;
     }
     if ((y < 0 || y >= h) && !reflect) {
@@ -394,7 +378,7 @@ __global__ void __launch_bounds__(NT) in_apply_rows_kernel(fg_view src, const fl
                 } else if (split_slot) {
                     store_presplit(drow + (size_t)xp * C, o, ss, c4 & 1);
                 } else if (!HEAD || dst.ptr) {      // the fused head may skip its activation (dst null)
-                    am = max(am, absbits4(o));
+                    am = max(am, fg::abs_bits(o));
                     *reinterpret_cast<f32x4*>(drow + (size_t)xp * C) = o;
                     if (psrow) store_presplit(psrow + (size_t)xp * C, o, ss, c4 & 1);
                 }
@@ -405,7 +389,7 @@ __global__ void __launch_bounds__(NT) in_apply_rows_kernel(fg_view src, const fl
             }
         }
     }
-    if (amax) absmax_flush(am, amax);
+    if (amax) fg::raise_block_max<NT>(amax, am);
 }
 
 // ---- backward ----
@@ -537,7 +521,7 @@ __global__ void __launch_bounds__(NT) in_bwd_stats_u_kernel(fg_view g, int fp, f
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) gk[e] *= fg::act_grad(xh[e], act);
-                gm = max(gm, absbits4(gk));
+                gm = max(gm, fg::abs_bits(gk));
                 sg += gk;
                 sgx += gk * xh;
                 sx += xh;
@@ -545,15 +529,8 @@ __global__ void __launch_bounds__(NT) in_bwd_stats_u_kernel(fg_view g, int fp, f
         }
     }
     if (gmax_part) {     // this block's max |g'| (the pre-split output's scale bound, fg_in_bwd_presplit)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) gm = max(gm, (unsigned)__shfl_xor((int)gm, off));
-        __shared__ unsigned gred[NT / 64];
-        if ((threadIdx.x & 63) == 0) gred[threadIdx.x >> 6] = gm;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int i = 1; i < NT / 64; ++i) gm = max(gm, gred[i]);
-            gmax_part[n * chunks + chunk] = __uint_as_float(gm);
-        }
+        gm = fg::block_max<NT, fg::kOnce>(gm);
+        if (threadIdx.x == 0) gmax_part[n * chunks + chunk] = __uint_as_float(gm);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -690,9 +667,10 @@ __global__ void __launch_bounds__(kFinC * kFinS) in_bwd_finalize_kernel(int N, i
                                                                         float* __restrict__ split_slot) {
     const int n = blockIdx.x, cl = threadIdx.x % kFinC, sl = threadIdx.x / kFinC, c = blockIdx.y * kFinC + cl;
     __shared__ double red[kFinS][kFinC][3];
-    __shared__ unsigned gmx, bmx;
+    __shared__ unsigned gmx;
+    unsigned bm = 0;     // this thread's bound of its plane's output (pre-split output)
     if (split_slot) {
-        if (threadIdx.x == 0) gmx = bmx = 0;
+        if (threadIdx.x == 0) gmx = 0;
         __syncthreads();
         unsigned m = 0;
         for (int k = threadIdx.x; k < chunks; k += blockDim.x) m = max(m, __float_as_uint(gmax_part[n * chunks + k]));
@@ -751,19 +729,15 @@ __global__ void __launch_bounds__(kFinC * kFinS) in_bwd_finalize_kernel(int N, i
         if (split_slot) {
             // |rstd (g' - c1 - xhat c2)| <= rstd (max|g'| + |c1| + sqrt(HW - 1) |c2|), with rounding slack
             const float b = rstd[idx] * (__uint_as_float(gmx) + fabsf(c1) + sqrtf((float)(HWi - 1)) * fabsf(c2)) * 1.001f;
-            atomicMax(&bmx, __float_as_uint(b));
+            bm = __float_as_uint(b);
         }
     }
-    if (split_slot) {
-        __syncthreads();
-        if (threadIdx.x == 0)
-            atomicMax(reinterpret_cast<unsigned*>(split_slot) + ((n * gridDim.y + blockIdx.y) & (FG_AMAX_SHARDS - 1)), bmx);
-    }
+    if (split_slot) fg::raise_block_max<kFinC * kFinS>(split_slot, bm, n * gridDim.y + blockIdx.y);
 }
 
 __global__ void in_bwd_apply_kernel(fg_view g, int fp, fg_view gadd, fg_view src, const float* __restrict__ mean,
                                     const float* __restrict__ rstd, const float* __restrict__ coef, int act,
-                                    fg_view dst, unsigned* __restrict__ amax, const double* __restrict__ bpart,
+                                    fg_view dst, float* __restrict__ amax, const double* __restrict__ bpart,
                                     float* __restrict__ bias_grad, int bias_accumulate) {
     // block 0 also sums the per-plane bias-gradient parts of the finalize over the images (the finalize
     // has completed: kernel boundary) -- no launch of its own for a few hundred values
@@ -801,10 +775,10 @@ __global__ void in_bwd_apply_kernel(fg_view g, int fp, fg_view gadd, fg_view src
                 out[e] = r[e] * (gp - coef[(nc + e) * 2] - xh[e] * coef[(nc + e) * 2 + 1]);
             }
         }
-        am = max(am, absbits4(out));
+        am = max(am, fg::abs_bits(out));
         *reinterpret_cast<f32x4*>(dst.ptr + ((size_t)(n * hp + yp) * wp + xp) * C + 4 * c4) = out;
     }
-    if (amax) absmax_flush(am, amax);
+    if (amax) fg::raise_block_max<NT>(amax, am);
 }
 
 // row form of the backward apply (C/4 | 256): block = one padded output row, kRowU pixels' loads in flight
@@ -813,13 +787,13 @@ __global__ void __launch_bounds__(NT) in_bwd_apply_rows_kernel(fg_view g, int fp
                                                                const float* __restrict__ mean,
                                                                const float* __restrict__ rstd,
                                                                const float* __restrict__ coef, int act, fg_view dst,
-                                                               unsigned* __restrict__ amax,
+                                                               float* __restrict__ amax,
                                                                const double* __restrict__ bpart,
                                                                float* __restrict__ bias_grad, int bias_accumulate,
                                                                int lshift, const float* __restrict__ split_slot,
                                                                HeadArgs hd = HeadArgs{}) {
     // pre-split output: the scale of the bound the finalize published (the consumer derives the same one)
-    const float ss = split_slot ? fgc::pow2_scale(split_slot) : 0.f;
+    const float ss = split_slot ? fg::pow2_scale(split_slot) : 0.f;
     if (bias_grad && blockIdx.x == 0) {
         const int C = dst.c_alloc;
         for (int c = threadIdx.x; c < C; c += blockDim.x) {
@@ -882,17 +856,17 @@ __global__ void __launch_bounds__(NT) in_bwd_apply_rows_kernel(fg_view g, int fp
                 if (split_slot) {
                     store_presplit(drow + (size_t)xp * C, out, ss, c4 & 1);
                 } else {
-                    am = max(am, absbits4(out));
+                    am = max(am, fg::abs_bits(out));
                     *reinterpret_cast<f32x4*>(drow + (size_t)xp * C) = out;
                 }
             }
         }
     }
-    if (amax) absmax_flush(am, amax);
+    if (amax) fg::raise_block_max<NT>(amax, am);
 }
 
 // float4 form: block = interior row (n, yy), threads over (x, channel quad) of the row
-__global__ void __launch_bounds__(256) act_bwd4_kernel(fg_view g, fg_view y, int act, unsigned* __restrict__ amax) {
+__global__ void __launch_bounds__(256) act_bwd4_kernel(fg_view g, fg_view y, int act, float* __restrict__ amax) {
     unsigned am = 0;
     const int C = g.c_alloc, C4 = C / 4, W4 = g.w * C4;
     const int n = blockIdx.x / g.h, yy = blockIdx.x - (blockIdx.x / g.h) * g.h;
@@ -904,13 +878,13 @@ __global__ void __launch_bounds__(256) act_bwd4_kernel(fg_view g, fg_view y, int
         const f32x4 yv = ld4(yrow + (size_t)x * C + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) gv[e] *= fg::act_grad(yv[e], act);
-        am = max(am, absbits4(gv));
+        am = max(am, fg::abs_bits(gv));
         *reinterpret_cast<f32x4*>(grow + (size_t)x * C + c) = gv;
     }
-    if (amax) absmax_flush(am, amax);
+    if (amax) fg::raise_block_max<NT, fg::kOnce>(amax, am);
 }
 
-__global__ void act_bwd_kernel(fg_view g, fg_view y, int act, unsigned* __restrict__ amax) {
+__global__ void act_bwd_kernel(fg_view g, fg_view y, int act, float* __restrict__ amax) {
     unsigned am = 0;
     const int C = g.c_alloc;
     const long long total = (long long)g.n * g.h * g.w * C;
@@ -924,10 +898,10 @@ __global__ void act_bwd_kernel(fg_view g, fg_view y, int act, unsigned* __restri
         const int n = (int)(pix / g.h);
         const float yv = y.ptr[fg::vidx(y, n, yy, x) + c];
         const float v = g.ptr[fg::vidx(g, n, yy, x) + c] * fg::act_grad(yv, act);
-        am = max(am, __float_as_uint(v) & 0x7fffffffu);
+        am = max(am, fg::abs_bits(v));
         g.ptr[fg::vidx(g, n, yy, x) + c] = v;
     }
-    if (amax) absmax_flush(am, amax);
+    if (amax) fg::raise_block_max<NT>(amax, am);
 }
 
 __global__ void channel_sum_kernel(fg_view src, int c_valid, int chunks, double* __restrict__ work) {
@@ -1311,20 +1285,20 @@ int in_apply_impl(fg_view src, const float* mean, const float* rstd, int act, fg
     if (head) {
         auto kern = in_nt2_on() ? in_apply_rows_kernel<true, true> : in_apply_rows_kernel<false, true>;
         hipLaunchKernelGGL(kern, dim3(dst.n * (dst.h + 2 * dst.pad)), dim3(NT), 0, stream, src, mean, rstd, act,
-                           residual, dst, pad_mode, ilog2(C4), reinterpret_cast<unsigned*>(absmax), split_slot, ps_ptr,
+                           residual, dst, pad_mode, ilog2(C4), absmax, split_slot, ps_ptr,
                            ps_slot, res_amax, splitpix, *head);
         return fg::launched("in_apply_rows_head");
     }
     if ((g_in_rows || split_slot || ps_ptr) && NT % C4 == 0) {
         auto kern = in_nt2_on() ? in_apply_rows_kernel<true> : in_apply_rows_kernel<false>;
         hipLaunchKernelGGL(kern, dim3(dst.n * (dst.h + 2 * dst.pad)), dim3(NT), 0, stream, src, mean,
-                           rstd, act, residual, dst, pad_mode, ilog2(C4), reinterpret_cast<unsigned*>(absmax),
+                           rstd, act, residual, dst, pad_mode, ilog2(C4), absmax,
                            split_slot, ps_ptr, ps_slot, res_amax, splitpix, HeadArgs{});
         return fg::launched("in_apply_rows");
     }
     const long long total = (long long)dst.n * (dst.h + 2 * dst.pad) * (dst.w + 2 * dst.pad) * (dst.c_alloc / 4);
     hipLaunchKernelGGL(in_apply_kernel, dim3(fg::blocks_for(total, 256, 4096)), dim3(256), 0, stream, src, mean,
-                       rstd, act, residual, dst, pad_mode, reinterpret_cast<unsigned*>(absmax));
+                       rstd, act, residual, dst, pad_mode, absmax);
     return fg::launched("in_apply");
 }
 }  // namespace
@@ -1396,7 +1370,7 @@ int in_bwd_impl(fg_view gsrc, int fold_pad, fg_view gadd, fg_view src, const flo
     if (head) {
         auto kern = in_nt2_on() ? in_bwd_apply_rows_kernel<true, true> : in_bwd_apply_rows_kernel<false, true>;
         hipLaunchKernelGGL(kern, dim3(dst.n * (dst.h + 2 * dst.pad)), dim3(NT), 0, stream, gsrc, 0, none, src, mean,
-                           rstd, coef, act, dst, reinterpret_cast<unsigned*>(absmax), bpart, bias_grad,
+                           rstd, coef, act, dst, absmax, bpart, bias_grad,
                            bias_accumulate, ilog2(C / 4), split_slot, *head);
         return fg::launched("in_bwd_apply_rows_head");
     }
@@ -1404,27 +1378,26 @@ int in_bwd_impl(fg_view gsrc, int fold_pad, fg_view gadd, fg_view src, const flo
         auto kern = in_nt2_on() ? in_bwd_apply_rows_kernel<true> : in_bwd_apply_rows_kernel<false>;
         hipLaunchKernelGGL(kern, dim3(dst.n * (dst.h + 2 * dst.pad)), dim3(NT), 0, stream,
                            gsum.ptr ? gsum : gsrc, gsum.ptr ? 0 : fold_pad, gsum.ptr ? none : gadd, src, mean, rstd,
-                           coef, act, dst, reinterpret_cast<unsigned*>(absmax), bpart, bias_grad, bias_accumulate,
+                           coef, act, dst, absmax, bpart, bias_grad, bias_accumulate,
                            ilog2(C / 4), split_slot, HeadArgs{});
         return fg::launched("in_bwd_apply_rows");
     }
     hipLaunchKernelGGL(in_bwd_apply_kernel, dim3(fg::blocks_for(total, 256, 4096)), dim3(256), 0, stream,
                        gsum.ptr ? gsum : gsrc, gsum.ptr ? 0 : fold_pad, gsum.ptr ? none : gadd, src, mean, rstd, coef,
-                       act, dst, reinterpret_cast<unsigned*>(absmax), bpart, bias_grad, bias_accumulate);
+                       act, dst, absmax, bpart, bias_grad, bias_accumulate);
     return fg::launched("in_bwd_apply");
 }
 }  // namespace
 
 FG_API int fg_act_bwd(fg_view g, fg_view y, int act, float* absmax, hipStream_t stream) {
-    unsigned* am = reinterpret_cast<unsigned*>(absmax);
     if (!ok_view(g) || !ok_view(y) || g.c_alloc != y.c_alloc || g.h != y.h || g.w != y.w || g.n != y.n)
         return fg::fail(FG_ERR_INVALID, "fg_act_bwd: bad args");
     if (g.c_alloc % 4 == 0) {
-        hipLaunchKernelGGL(act_bwd4_kernel, dim3(g.n * g.h), dim3(256), 0, stream, g, y, act, am);
+        hipLaunchKernelGGL(act_bwd4_kernel, dim3(g.n * g.h), dim3(256), 0, stream, g, y, act, absmax);
         return fg::launched("act_bwd4");
     }
     const long long total = (long long)g.n * g.h * g.w * g.c_alloc;
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(fg::blocks_for(total, 256, 16384)), dim3(256), 0, stream, g, y, act, am);
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(fg::blocks_for(total, 256, 16384)), dim3(256), 0, stream, g, y, act, absmax);
     return fg::launched("act_bwd");
 }
 

@@ -1,7 +1,7 @@
 // Losses of the paired step (models/model.py:626-644: nn.MSELoss vs constant 0/1 targets,
 // nn.L1Loss x100) with their gradients, and torch.optim.Adam (models/model.py:121-122)
 // as one multi-tensor kernel.  Reductions are two-stage and deterministic (fp64 partials).
-#include "fg_common.hpp"
+#include "amax_slot.hpp"
 
 namespace {
 
@@ -101,19 +101,9 @@ __global__ void adam_kernel(const AdamGroup G) {
         T.param[i] = np;
         T.exp_avg[i] = m;
         T.exp_avg_sq[i] = v;
-        amax = max(amax, __float_as_uint(np) & 0x7fffffffu);
+        amax = max(amax, fg::abs_bits(np));
     }
-    if (T.absmax) {     // bitwise max of |param| (uint order = float order), one shard per block
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, off));
-        __shared__ unsigned red[NT / 64];
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int i = 1; i < NT / 64; ++i) amax = max(amax, red[i]);
-            atomicMax(reinterpret_cast<unsigned*>(T.absmax) + (blockIdx.x & (FG_AMAX_SHARDS - 1)), amax);
-        }
-    }
+    if (T.absmax) fg::raise_block_max<NT>(T.absmax, amax);     // max |param| of this block's tensor
 }
 
 }  // namespace

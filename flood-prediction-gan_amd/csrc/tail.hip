@@ -3,7 +3,7 @@
 //     out[c] = sum_{i<9} tanh(cl[3i+c]) * att[i]  +  input[c] * att[9]
 // (summed left to right as the reference does) and last_attention_mask = att[9].
 // One thread per pixel; the backward recomputes tanh / softmax from the saved logits.
-#include "fg_common.hpp"
+#include "amax_slot.hpp"
 
 namespace {
 
@@ -69,21 +69,9 @@ __global__ void tail_fwd_kernel(fg_view cl, fg_view al, fg_sview x, float* __res
     }
 }
 
-// fold a thread's max |v| bits into shard blockIdx % FG_AMAX_SHARDS of an absmax slot (256-thread blocks)
-__device__ __forceinline__ void flush_amax(unsigned m, unsigned* out, unsigned* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(out + (blockIdx.x & (FG_AMAX_SHARDS - 1)), max(max(red[0], red[1]), max(red[2], red[3])));
-    __syncthreads();
-}
-
-__device__ __forceinline__ unsigned abits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-
 __global__ void __launch_bounds__(256) tail_bwd_kernel(fg_view cl, fg_view al, fg_sview x, fg_sview gout, fg_sview gmask,
-                                                       fg_view gc, fg_view ga, fg_wview gx, unsigned* amax_c,
-                                                       unsigned* amax_a) {
+                                                       fg_view gc, fg_view ga, fg_wview gx, float* amax_c,
+                                                       float* amax_a) {
     unsigned mc = 0, ma = 0;                      // max |g_content|, |g_att| written by this thread
     // iterate over gc's padded extent so its zero border is written too
     const int H = cl.h, W = cl.w;
@@ -123,7 +111,7 @@ __global__ void __launch_bounds__(256) tail_bwd_kernel(fg_view cl, fg_view al, f
 #pragma unroll
         for (int i = NCONT; i < 32; ++i) go[i] = 0.f;
 #pragma unroll
-        for (int i = 0; i < NCONT; ++i) mc = max(mc, abits(go[i]));
+        for (int i = 0; i < NCONT; ++i) mc = max(mc, fg::abs_bits(go[i]));
 #pragma unroll
         for (int q = 0; q < 8; ++q)
             *reinterpret_cast<f32x4*>(gcp + 4 * q) = f32x4{go[4 * q], go[4 * q + 1], go[4 * q + 2], go[4 * q + 3]};
@@ -145,15 +133,14 @@ __global__ void __launch_bounds__(256) tail_bwd_kernel(fg_view cl, fg_view al, f
 #pragma unroll
         for (int i = NATT; i < 16; ++i) ao[i] = 0.f;
 #pragma unroll
-        for (int i = 0; i < NATT; ++i) ma = max(ma, abits(ao[i]));
+        for (int i = 0; i < NATT; ++i) ma = max(ma, fg::abs_bits(ao[i]));
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             *reinterpret_cast<f32x4*>(gap + 4 * q) = f32x4{ao[4 * q], ao[4 * q + 1], ao[4 * q + 2], ao[4 * q + 3]};
         for (int i = 16; i < ga.c_alloc; i += 4) *reinterpret_cast<f32x4*>(gap + i) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    __shared__ unsigned red[4];
-    if (amax_c) flush_amax(mc, amax_c, red);
-    if (amax_a) flush_amax(ma, amax_a, red);
+    if (amax_c) fg::raise_block_max<256>(amax_c, mc);
+    if (amax_a) fg::raise_block_max<256>(amax_a, ma);
 }
 
 // CycleGAN head (models/model_architectures.py:115-117: conv 7x7 64->3 then nn.Tanh): one thread
@@ -231,7 +218,7 @@ FG_API int fg_tail_bwd(fg_view content_logits, fg_view att_logits, fg_sview x, f
                             (content_logits.w + 2 * g_content.pad);
     hipLaunchKernelGGL(tail_bwd_kernel, dim3(fg::blocks_for(total, 256, 16384)), dim3(256), 0, stream,
                        content_logits, att_logits, x, g_out, g_mask, g_content, g_att, g_x,
-                       reinterpret_cast<unsigned*>(absmax_content), reinterpret_cast<unsigned*>(absmax_att));
+                       absmax_content, absmax_att);
     return fg::launched("tail_bwd");
 }
 

@@ -801,7 +801,7 @@ def test_fused_in_stats(case, conv_math):
 
 def _decode_presplit(B, slot):
     """values of a FG_PRESPLIT buffer (include/floodgan.h): per 8 channels h[8] | l[8] of v * s, s the pow2
-    scale of the slot's max (pow2_of in conv_common.hpp)"""
+    scale of the slot's max (pow2_of in amax_slot.hpp)"""
     import math
     e = math.frexp(float(slot.max()))[1]
     s = 2.0 ** (14 - e)

@@ -124,6 +124,10 @@ def test_c_abi_library_exports_every_declared_symbol():
     assert declared == set(L.SIGNATURES), declared ^ set(L.SIGNATURES)
     assert lib.fg_version() >= 1
     assert lib.fg_in_workspace_doubles(8, 256) > 0
+    # the host's slot size mirrors the header's by hand (the device code takes it from the header: amax_slot.hpp)
+    from floodgan import ops
+    (shards,) = re.findall(r"^enum \{ FG_AMAX_SHARDS = (\d+) \};", header, re.M)
+    assert ops.SHARDS == int(shards)
 
 
 def test_no_module_reaches_into_a_siblings_private_names():
