@@ -84,6 +84,15 @@ FG_SCALAR_UNIT, FG_SCALAR_THRESHOLD, FG_SCALAR_LOGIT = 0, 1, 2
 class fg_canvas(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("row_bytes", C.c_longlong)]
 
+
+FG_MOSAIC_MAX_OVERLAP = 1024
+
+
+class fg_mosaic_grid(C.Structure):
+    _fields_ = [("ys", C.c_void_p), ("xs", C.c_void_p), ("ys_host", C.c_void_p), ("xs_host", C.c_void_p),
+                ("ny", C.c_int), ("nx", C.c_int), ("tile", C.c_int), ("overlap", C.c_int)]
+
+
 # fg_set_f3_order's default (csrc/conv_f3.hip g_f3_alt): tests restore it after sweeping the bits
 F3_ORDER_DEFAULT = 31
 
@@ -225,6 +234,9 @@ SIGNATURES = {
                       C.c_void_p],
     "fg_render_scalar": [fg_sview, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, fg_canvas, C.c_int, C.c_int,
                          C.c_int, C.c_int, C.c_void_p],
+    "fg_mosaic_accumulate": [fg_sview, C.c_int, C.c_int, fg_mosaic_grid, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                             C.c_void_p],
+    "fg_mosaic_finalize": [C.c_void_p, C.c_int, fg_mosaic_grid, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "fg_tiff_probe": [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "fg_tiff_read": [C.c_char_p, C.c_void_p, C.c_longlong],
     "fg_tile_transform": [C.POINTER(fg_tile_batch), C.c_void_p],

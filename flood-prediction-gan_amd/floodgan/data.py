@@ -331,6 +331,26 @@ def load_image_pair(image_name, data_path, dataset_dem, topography, resize, crop
     return xo, yo, f"{image_name}_{crop_index}" if crop else image_name
 
 
+def load_scene(path, topography, device="cuda"):
+    """A pre-flood scene of any size as floodgan.scene.predict_scene takes it: the TIFF at `path` decoded by
+    read_tile and put through the loader's device transform without resize, crop or flip (Normalize(0.5, 0.5) and the
+    topography's channels).  A 9-channel file is the full input stack and is narrowed through
+    TOPOGRAPHY_SOURCE_CHANNELS[topography]; a file that already has that topography's channel count is taken as it
+    is; any other count raises ValueError.  Returns [1, C, H, W] on the device, channels-last."""
+    chan = TOPOGRAPHY_SOURCE_CHANNELS[None if topography in (None, "none") else topography]
+    raw = read_tile(path)
+    h, w, c = raw.shape
+    if c != 9 and c != len(chan):
+        raise ValueError(f"load_scene: {path} has {c} channels; topography {topography!r} takes the 9-channel input "
+                         f"stack or a file of its own {len(chan)} channels")
+    if c != 9:
+        chan = list(range(c))
+    dev = torch.device(device)
+    out = torch.empty((1, len(chan), h, w), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    transform_batch(torch.from_numpy(raw)[None].to(dev), None, None, chan, None, None, out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ dataset
 
 class FloodDataset:

@@ -501,6 +501,43 @@ class Model:
                 print(f"Saving {name} image set to {path}")
         return written
 
+    def predict_scene(self, input_path, tile=None, overlap=64, batch=8, seg_model_path=None, batch_stats=False,
+                      out_dir=None):
+        """Not in the reference: the predicted post-flood picture of a whole pre-flood scene, a TIFF of any size that
+        need not be a dataset tile (floodgan.data.load_scene, floodgan.scene.predict_scene: overlapping windows
+        through the generator -- pre_to_post for the cycle models -- blended on the device).  tile=None: the size the
+        model was built for (resize when set, else 512).  Writes {out_dir}/{name}_prediction.png (out_dir defaults
+        to {data_path}/images) and, with seg_model_path (a checkpoint path, a SegmentationModel or a UNet), the flood
+        mask of the blended segmentation logits as {name}_floodMask.png.  Returns {"prediction": path, "flood_mask":
+        path or None, "flood_fraction": float or None, "grid": (ys, xs)}.  Out of scope: attention-mask mosaics,
+        reflect-padding of scenes smaller than a window, GeoTIFF output."""
+        import os
+
+        from .data import load_scene
+        from .render import save_image
+        from .scene import predict_scene, scene_name
+        if out_dir is None:
+            if self.data_path is None:
+                raise ValueError("predict_scene: pass out_dir (the default is {data_path}/images and this Model has "
+                                 "no data_path)")
+            out_dir = f"{self.data_path}/images"
+        if tile is None:
+            tile = self.resize if self.resize else 512
+        x = load_scene(input_path, self.topography, self.device)
+        generator = self.pre_to_post_generator if self.model_is_cycle else self.generator
+        res = predict_scene(generator, x, tile=tile, overlap=overlap, batch=batch, seg_model=seg_model_path,
+                            batch_stats=batch_stats)
+        os.makedirs(out_dir, exist_ok=True)
+        name = scene_name(input_path)
+        written = {"prediction": save_image(f"{out_dir}/{name}_prediction.png", res["output"], "rgb"),
+                   "flood_mask": None, "flood_fraction": res.get("flood_fraction"), "grid": res["grid"]}
+        if "flood_logits" in res:
+            written["flood_mask"] = save_image(f"{out_dir}/{name}_floodMask.png", res["flood_logits"], "mask_logits")
+        if self.verbose:
+            print(f"Saving the prediction of scene '{name}' to {written['prediction']}")
+        self.last_scene = res
+        return written
+
     def _sheet_columns(self, inputs, outputs, masks, targets):
         cols = [("Input", "rgb", inputs), ("Generator Output", "rgb", outputs)]
         if masks is not None:

@@ -1111,3 +1111,63 @@ def render_scalar(t, lut, canvas, row=0, col=0, kind="unit", step_rows=0, step_c
         raise RuntimeError("floodgan render_scalar: the colour table is a contiguous uint8 [256, 4] device tensor")
     L.check(L.load().fg_render_scalar(sview(t), n, h, w, RENDER_SCALAR_KINDS[kind], L.ptr(lut), canvas_struct(canvas),
                                       row, col, step_rows, step_cols, L.stream_handle()), "render_scalar")
+
+
+# ------------------------------------------------------------------------------------------ scenes (mosaic.hip)
+
+def mosaic_grid_struct(ys, xs, ys_host, xs_host, tile, overlap):
+    """fg_mosaic_grid of the window starts: ys / xs int32 device tensors, ys_host / xs_host the same values as
+    contiguous int32 numpy arrays (the entry checks read those; the caller keeps all four alive)"""
+    for dev, host in ((ys, ys_host), (xs, xs_host)):
+        if not (dev.is_cuda and dev.dtype == torch.int32 and dev.is_contiguous() and dev.dim() == 1
+                and host.dtype.name == "int32" and host.flags["C_CONTIGUOUS"] and host.shape == tuple(dev.shape)):
+            raise RuntimeError("floodgan mosaic: window starts are a contiguous int32 device tensor and its int32 "
+                               "numpy copy")
+    return L.fg_mosaic_grid(ys.data_ptr(), xs.data_ptr(), ys_host.ctypes.data, xs_host.ctypes.data, ys.numel(),
+                            xs.numel(), int(tile), int(overlap))
+
+
+def _mosaic_planes(planes, what):
+    L.require_device(planes, what)
+    if planes.dim() != 3 or not planes.is_contiguous():
+        raise RuntimeError(f"floodgan mosaic: {what} are a contiguous fp32 [c, H, W] tensor (got "
+                           f"{tuple(planes.shape)})")
+    return planes.shape
+
+
+def mosaic_accumulate(windows, k0, grid, planes):
+    """fg_mosaic_accumulate: adds the weighted windows k0 .. k0 + n - 1 of `grid` (mosaic_grid_struct) into planes
+    (fp32 [c, H, W], contiguous).  windows: [n, >= c, tile, tile] with any strides, or an NHWC Buf (its channels
+    0 .. c - 1)."""
+    t = _render_source(windows, "windows")
+    c, H, W = _mosaic_planes(planes, "accumulation planes")
+    if t.dim() != 4 or t.shape[1] < c or t.shape[2] != grid.tile or t.shape[3] != grid.tile:
+        raise RuntimeError(f"floodgan mosaic_accumulate: need [n, >= {c}, {grid.tile}, {grid.tile}] windows (got "
+                           f"{tuple(t.shape)})")
+    wrote(planes)
+    L.check(_lib().fg_mosaic_accumulate(sview(t), t.shape[0], c, grid, int(k0), L.ptr(planes), H, W,
+                                        L.stream_handle()), "mosaic_accumulate")
+
+
+def mosaic_finalize(planes, grid, out):
+    """fg_mosaic_finalize: out [1, c, H, W] (contiguous fp32) = planes / the pixels' weight sums"""
+    c, H, W = _mosaic_planes(planes, "accumulation planes")
+    L.require_device(out, "blended image")
+    if tuple(out.shape) != (1, c, H, W) or not out.is_contiguous():
+        raise RuntimeError(f"floodgan mosaic_finalize: the result is a contiguous [1, {c}, {H}, {W}] tensor (got "
+                           f"{tuple(out.shape)})")
+    wrote(out)
+    L.check(_lib().fg_mosaic_finalize(L.ptr(planes), c, grid, H, W, L.ptr(out), L.stream_handle()), "mosaic_finalize")
+
+
+def flood_count(logits):
+    """the number of flood pixels of a contiguous fp32 [N, 1, H, W] logits tensor as an int64 device scalar: the true
+    positives of fg_mask_confusion of the logits against themselves (the package's one flood decision)"""
+    L.require_device(logits, "flood logits")
+    if logits.dim() != 4 or logits.shape[1] != 1 or not logits.is_contiguous():
+        raise RuntimeError(f"floodgan flood_count: a contiguous [N, 1, H, W] tensor (got {tuple(logits.shape)})")
+    n, _, h, w = logits.shape
+    v = L.fg_view(logits.data_ptr(), n, h, w, 1, 0)
+    counts = torch.zeros(4, dtype=torch.int64, device=logits.device)
+    L.check(_lib().fg_mask_confusion(v, v, L.ptr(counts), L.stream_handle()), "mask_confusion")
+    return counts[0]

@@ -694,6 +694,45 @@ int fg_render_scalar(fg_sview src, int n, int h, int w, int mode, const unsigned
                      int col0, int step_rows, int step_cols, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------- */
+/* scenes: windowed inference with overlap blending (floodgan/scene.py; not in the reference, */
+/* whose only answer to an image larger than a tile is the quadrant crop)                    */
+/* ---------------------------------------------------------------------------------------- */
+/* The window grid of an H x W scene: ny x nx square windows of `tile` pixels, window k = iy * nx + ix with its
+ * top-left pixel at (ys[iy], xs[ix]).  Along an axis of length L the starts are the ascending values min(i * S,
+ * L - tile), S = tile - overlap: every window lies inside the scene, the last one shifted inward.  0 <= overlap <=
+ * min(tile / 2, FG_MOSAIC_MAX_OVERLAP), so at most three windows cover a coordinate along one axis.  ys / xs are device
+ * int32 arrays, which the kernels read; ys_host / xs_host are the same values in host memory, which the entry checks
+ * read (no call waits for the device).  The kernels index a window only at local coordinates inside it and the scene
+ * only at pixels inside it, whatever the device arrays hold.
+ * The weight of window-local coordinate u is the integer w(u) = min(u + 1, tile - u, max(overlap, 1)); a pixel's
+ * weight in a window is w(y - y0) * w(x - x0) <= 2^20, and a pixel's weight sum over its <= 9 windows is below 2^24:
+ * weights and weight sums are exact in fp32. */
+enum { FG_MOSAIC_MAX_OVERLAP = 1024 };
+typedef struct fg_mosaic_grid {
+    const int* ys;
+    const int* xs;
+    const int* ys_host;
+    const int* xs_host;
+    int ny, nx, tile, overlap;
+} fg_mosaic_grid;
+/* planes[ch, y, x] += w_k(y, x) * src[k - k0, ch, y - y0_k, x - x0_k] for the windows k = k0 .. k0 + n - 1 of the grid
+ * that cover (y, x), ch < c (c = 1 or 3): src a strided [n, >= c, tile, tile] view (a generator's channels-last output;
+ * channel 0 of the U-Net's NHWC logits), planes contiguous fp32 [c, H, W], zero before the first call.  Gather form:
+ * one lane owns a run of pixels of the scene region the batch touches and adds its windows' contributions in
+ * ascending k, the product and the add as separate fp32 operations; no atomics.  The chain of operations a pixel
+ * sees is therefore the same however the windows 0 .. ny nx - 1 are split into calls of ascending k0: the planes
+ * are bit-identical for every such split.  Pixels no window of the batch covers are not written.
+ * Fails (FG_ERR_INVALID, nothing written) on a null pointer, a size that is not positive, c other than 1 or 3, an
+ * overlap outside the bounds above, tile > H or W, starts (host copy) that are not ascending, leave the scene or
+ * leave a pixel uncovered, or k0 < 0 or k0 + n > ny nx. */
+int fg_mosaic_accumulate(fg_sview src, int n, int c, fg_mosaic_grid grid, int k0, float* planes, int H, int W,
+                         hipStream_t stream);
+/* dst[0, ch, y, x] = planes[ch, y, x] / sum_k w_k(y, x) (one fp32 division; dst contiguous NCHW [1, c, H, W]).  The
+ * weight sum is recomputed from the grid as an integer -- (sum of w over the covering rows) * (sum of w over the
+ * covering columns) -- and converted once: there is no weight plane in memory.  Fails as fg_mosaic_accumulate. */
+int fg_mosaic_finalize(const float* planes, int c, fg_mosaic_grid grid, int H, int W, float* dst, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------- */
 /* tile data path                                                    */
 /* ---------------------------------------------------------------------------------------- */
 /* Host-side baseline TIFF decode, replacing tifffile.imread (models/data.py:64-68) for the files
