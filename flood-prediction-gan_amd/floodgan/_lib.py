@@ -86,6 +86,7 @@ class fg_canvas(C.Structure):
 
 
 FG_MOSAIC_MAX_OVERLAP = 1024
+FG_REGIONS_REMOVE, FG_REGIONS_FILL = 0, 1
 
 
 class fg_mosaic_grid(C.Structure):
@@ -237,6 +238,11 @@ SIGNATURES = {
     "fg_mosaic_accumulate": [fg_sview, C.c_int, C.c_int, fg_mosaic_grid, C.c_int, C.c_void_p, C.c_int, C.c_int,
                              C.c_void_p],
     "fg_mosaic_finalize": [C.c_void_p, C.c_int, fg_mosaic_grid, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "fg_regions_label": [fg_sview, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "fg_regions_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fg_regions_table": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p],
+    "fg_regions_apply": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                         C.c_void_p, C.c_void_p],
     "fg_tiff_probe": [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "fg_tiff_read": [C.c_char_p, C.c_void_p, C.c_longlong],
     "fg_tile_transform": [C.POINTER(fg_tile_batch), C.c_void_p],

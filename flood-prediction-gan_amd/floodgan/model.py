@@ -502,15 +502,19 @@ class Model:
         return written
 
     def predict_scene(self, input_path, tile=None, overlap=64, batch=8, seg_model_path=None, batch_stats=False,
-                      out_dir=None):
+                      out_dir=None, min_region=None, min_hole=None, connectivity=8):
         """Not in the reference: the predicted post-flood picture of a whole pre-flood scene, a TIFF of any size that
         need not be a dataset tile (floodgan.data.load_scene, floodgan.scene.predict_scene: overlapping windows
         through the generator -- pre_to_post for the cycle models -- blended on the device).  tile=None: the size the
         model was built for (resize when set, else 512).  Writes {out_dir}/{name}_prediction.png (out_dir defaults
         to {data_path}/images) and, with seg_model_path (a checkpoint path, a SegmentationModel or a UNet), the flood
         mask of the blended segmentation logits as {name}_floodMask.png.  Returns {"prediction": path, "flood_mask":
-        path or None, "flood_fraction": float or None, "grid": (ys, xs)}.  Out of scope: attention-mask mosaics,
-        reflect-padding of scenes smaller than a window, GeoTIFF output."""
+        path or None, "flood_fraction": float or None, "grid": (ys, xs)}.  With min_region / min_hole (either given; they
+        need seg_model_path) the mask is sieved (floodgan.regions: flood components below min_region pixels removed,
+        enclosed holes below min_hole filled, `connectivity` 8 or 4 for the flood class): {name}_floodMask.png is then
+        the sieved mask, {name}_floodRegions.csv beside it lists the regions, and the returned dict gains "regions"
+        (the CSV's path) and "region_count".  Out of scope: attention-mask mosaics, reflect-padding of scenes smaller
+        than a window, GeoTIFF output."""
         import os
 
         from .data import load_scene
@@ -526,12 +530,18 @@ class Model:
         x = load_scene(input_path, self.topography, self.device)
         generator = self.pre_to_post_generator if self.model_is_cycle else self.generator
         res = predict_scene(generator, x, tile=tile, overlap=overlap, batch=batch, seg_model=seg_model_path,
-                            batch_stats=batch_stats)
+                            batch_stats=batch_stats, min_region=min_region, min_hole=min_hole,
+                            connectivity=connectivity)
         os.makedirs(out_dir, exist_ok=True)
         name = scene_name(input_path)
         written = {"prediction": save_image(f"{out_dir}/{name}_prediction.png", res["output"], "rgb"),
                    "flood_mask": None, "flood_fraction": res.get("flood_fraction"), "grid": res["grid"]}
-        if "flood_logits" in res:
+        if "flood_mask" in res:
+            from .regions import write_regions_csv
+            written["flood_mask"] = save_image(f"{out_dir}/{name}_floodMask.png", res["flood_mask"], "mask_true")
+            written["regions"] = write_regions_csv(f"{out_dir}/{name}_floodRegions.csv", res["regions"])
+            written["region_count"] = res["regions"]["count"]
+        elif "flood_logits" in res:
             written["flood_mask"] = save_image(f"{out_dir}/{name}_floodMask.png", res["flood_logits"], "mask_logits")
         if self.verbose:
             print(f"Saving the prediction of scene '{name}' to {written['prediction']}")

@@ -1171,3 +1171,76 @@ def flood_count(logits):
     counts = torch.zeros(4, dtype=torch.int64, device=logits.device)
     L.check(_lib().fg_mask_confusion(v, v, L.ptr(counts), L.stream_handle()), "mask_confusion")
     return counts[0]
+
+
+# ------------------------------------------------------------------------------------------ flood regions (regions.hip)
+
+REGION_KINDS = {"threshold": L.FG_SCALAR_THRESHOLD, "logit": L.FG_SCALAR_LOGIT}
+REGION_MODES = {"remove": L.FG_REGIONS_REMOVE, "fill": L.FG_REGIONS_FILL}
+
+
+def _int_plane(t, H, W, what, dtype=torch.int32):
+    if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (H, W) and t.is_contiguous()):
+        raise RuntimeError(f"floodgan regions: {what} is a contiguous {dtype} [{H}, {W}] device tensor (got "
+                           f"{t.dtype} {tuple(t.shape)} on {t.device})")
+    return t
+
+
+def region_source(t):
+    """[H, W], [1, 1, H, W], channel 0 of [1, C, H, W] or of an NHWC Buf -> the [1, C, H, W] view the kernels read"""
+    t = _render_source(t, "region source")
+    if t.dim() == 2:
+        t = t[None, None]
+    if t.dim() != 4 or t.shape[0] != 1:
+        raise RuntimeError(f"floodgan regions: need [H, W] or [1, C, H, W] (got {tuple(t.shape)})")
+    return t
+
+
+def regions_label(src, kind, target, connectivity, labels):
+    """fg_regions_label: labels (int32 [H, W]) = the smallest pixel index of each pixel's component of the class
+    `target` of channel 0 of src ([1, C, H, W], any strides), -1 on the other class"""
+    _, _, H, W = src.shape
+    L.require_device(src, "region source")
+    _int_plane(labels, H, W, "the labels plane")
+    L.check(_lib().fg_regions_label(sview(src), H, W, REGION_KINDS[kind], int(bool(target)), int(connectivity),
+                                    L.ptr(labels), L.stream_handle()), "regions_label")
+    return labels
+
+
+def regions_stats(labels, area, border):
+    """fg_regions_stats: area / border (int32 [H, W]) at every root's index, 0 elsewhere"""
+    H, W = labels.shape
+    for t, what in ((labels, "the labels plane"), (area, "the area plane"), (border, "the border plane")):
+        _int_plane(t, H, W, what)
+    L.check(_lib().fg_regions_stats(L.ptr(labels), H, W, L.ptr(area), L.ptr(border), L.stream_handle()),
+            "regions_stats")
+
+
+def regions_table(labels, rank, table):
+    """fg_regions_table: table (int64 [R, 8]) from the labels and the rank plane"""
+    H, W = labels.shape
+    _int_plane(labels, H, W, "the labels plane")
+    _int_plane(rank, H, W, "the rank plane")
+    if not (table.is_cuda and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 8
+            and table.is_contiguous()):
+        raise RuntimeError("floodgan regions: the table is a contiguous int64 [R, 8] device tensor")
+    L.check(_lib().fg_regions_table(L.ptr(labels), L.ptr(rank), H, W, L.ptr(table), table.shape[0],
+                                    L.stream_handle()), "regions_table")
+
+
+def regions_apply(labels, area, border, mode, min_area, mask, counts):
+    """fg_regions_apply: one sieve step ("remove" / "fill") into mask (fp32 [H, W] or [1, 1, H, W], contiguous);
+    counts (int64 [2]) = components and pixels changed"""
+    H, W = labels.shape
+    _int_plane(labels, H, W, "the labels plane")
+    for t, what in ((area, "the area plane"), (border, "the border plane")):
+        if t is not None:
+            _int_plane(t, H, W, what)
+    L.require_device(mask, "region mask")
+    if mask.numel() != H * W or tuple(mask.shape[-2:]) != (H, W) or not mask.is_contiguous():
+        raise RuntimeError(f"floodgan regions: the mask is a contiguous fp32 [{H}, {W}] tensor (got {tuple(mask.shape)})")
+    if not (counts.is_cuda and counts.dtype == torch.int64 and tuple(counts.shape) == (2,) and counts.is_contiguous()):
+        raise RuntimeError("floodgan regions: counts is an int64 [2] device tensor")
+    wrote(mask)
+    L.check(_lib().fg_regions_apply(L.ptr(labels), L.ptr(area), L.ptr(border), H, W, REGION_MODES[mode], int(min_area),
+                                    L.ptr(mask), L.ptr(counts), L.stream_handle()), "regions_apply")

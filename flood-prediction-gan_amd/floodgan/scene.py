@@ -9,7 +9,8 @@ device (csrc/mosaic.hip: fg_mosaic_accumulate, fg_mosaic_finalize).  Not in the 
   window_grid    the window starts of an H x W scene: exact integer arithmetic (the CPU tests cover it)
   window_weight  the integer blending weight of a window-local coordinate
   Mosaic         the fp32 accumulation planes and the device grid: .windows / .add / .result
-  predict_scene  scene -> generator output, and with a segmentation U-Net its flood logits and flood fraction
+  predict_scene  scene -> generator output, and with a segmentation U-Net its flood logits and flood fraction; with
+                 min_region / min_hole also the sieved flood mask and its regions (floodgan.regions)
 
 Grid.  Along an axis of length L, with S = tile - overlap, the starts are the sorted unique values of
 min(i S, L - tile), i = 0 .. ceil((L - tile) / S): every window lies inside the scene, the last one shifted inward
@@ -153,7 +154,8 @@ def _flood_logits(unet, images, batch_stats):
                        update_running=False)
 
 
-def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, batch_stats=False):
+def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, batch_stats=False, min_region=None,
+                  min_hole=None, connectivity=8):
     """A device scene x [1, C, H, W] in [-1, 1] through `generator` in windows of tile x tile pixels, `batch` at a
     time (the last batch may be smaller), blended by Mosaic.  Runs under torch.no_grad() with torch.manual_seed(47)
     before each generator call, as the package's picture paths do; the generator runs in the mode it is in.
@@ -165,6 +167,10 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
     buffers are never written.  tile must then be a multiple of 16 (ValueError before any launch).
     A scene that is exactly one window returns the generator's output as it is, without a blend.  tile=None: one
     window over the whole scene, whatever its shape (the generator's own size check applies).
+    min_region / min_hole (either given, with seg_model; ValueError without): the flood-extent product of the blended
+    logits (floodgan.regions.flood_regions with the minima -- None is "off" -- and `connectivity`): the result gains
+    "flood_mask" (fp32 [1, 1, H, W] of 0 / 1, sieved), "regions" (flood_regions' dict without its mask) and
+    "flood_fraction_sieved"; "flood_logits" and "flood_fraction" are what they are without the minima.
     Out of scope: attention-mask mosaics, reflect-padding of scenes smaller than a window, GeoTIFF output."""
     require_device(x, "scene")
     if x.dim() != 4 or x.shape[0] != 1:
@@ -175,6 +181,14 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
     whole = tile is None
     ys, xs = ([0], [0]) if whole else window_grid(H, W, tile, overlap)
     unet = None
+    sieve = min_region is not None or min_hole is not None
+    if sieve:
+        if seg_model is None:
+            raise ValueError("predict_scene: min_region / min_hole sieve the flood mask and need seg_model")
+        min_region, min_hole = 1 if min_region is None else int(min_region), 0 if min_hole is None else int(min_hole)
+        if min_region < 0 or min_hole < 0 or connectivity not in (4, 8):
+            raise ValueError(f"predict_scene: min_region {min_region} and min_hole {min_hole} must not be negative, "
+                             f"connectivity {connectivity!r} must be 4 or 8")
     if seg_model is not None:
         for name, v in (("H", H), ("W", W)) if whole else (("tile", tile),):
             if v % 16:
@@ -207,6 +221,12 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
                 logits = ml.result()
             res["flood_logits"] = logits
             res["flood_fraction"] = int(ops.flood_count(logits).cpu()) / (H * W)
+            if sieve:
+                from .regions import flood_regions
+                regions = flood_regions(logits, "logit", min_region, min_hole, connectivity)
+                res["flood_mask"] = regions.pop("mask")
+                res["regions"] = regions
+                res["flood_fraction_sieved"] = regions["flood_fraction"]
     return res
 
 

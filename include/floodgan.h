@@ -733,6 +733,47 @@ int fg_mosaic_accumulate(fg_sview src, int n, int c, fg_mosaic_grid grid, int k0
 int fg_mosaic_finalize(const float* planes, int c, fg_mosaic_grid grid, int H, int W, float* dst, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------- */
+/* flood regions: labelling, statistics, sieve (not in the reference)         */
+/* ---------------------------------------------------------------------------------------- */
+/* All of it is integer-exact.  A pixel of an H x W scene has the index i = y * W + x; indices and labels are int32,
+ * so every entry refuses H * W >= 2^31.  The flood decision of a source value v is fg_render_scalar's:
+ * FG_SCALAR_LOGIT sigmoid(v) > 0.5 in fp32, the device function of fg_mask_confusion (+0, -0 and NaN are dry, +inf
+ * is flood); FG_SCALAR_THRESHOLD v > 0.5.  `connectivity` (4 or 8) is that of the FLOOD class; the dry class is
+ * labelled with the complementary one (8 against 4, 4 against 8).  Every entry fails with FG_ERR_INVALID and writes
+ * nothing on a null pointer it needs, a size that is not positive or too large, a misaligned pointer or an unknown
+ * kind, target, connectivity or mode.  Indices the kernels read from device memory (labels, ranks) are checked
+ * against the plane or table they index before use.
+ *
+ * fg_regions_label: labels[i] = the smallest index of the connected component of pixel i among the pixels of the
+ * class `target` (1 flood, 0 dry) -- the component's first pixel in row-major order -- and -1 for the pixels of the
+ * other class.  src: channel 0 of a strided view (sy, sx used; the mosaic's contiguous plane, channel 0 of NHWC
+ * logits); labels: contiguous int32 [H, W].  Union-find, three launches whatever the data: tiles of 16 x 64 pixels
+ * in LDS, the tile borders on the global plane with atomic min, path compression.  A union hangs the larger root
+ * under the smaller index, so the result depends on the mask alone, not on the schedule. */
+int fg_regions_label(fg_sview src, int H, int W, int kind, int target, int connectivity, int* labels,
+                     hipStream_t stream);
+/* Per component of a labels plane, at the root's index: area[root] = its pixel count, border[root] = 1 when it holds
+ * a pixel of the scene's first or last row or column, else 0; both planes (contiguous int32 [H, W]) are 0 at every
+ * other index.  Integer atomics, aggregated per lane run and per wave first. */
+int fg_regions_stats(const int* labels, int H, int W, int* area, int* border, hipStream_t stream);
+/* The region table: rank (contiguous int32 [H, W]) holds at every root's index the row 0 .. R - 1 of that
+ * component (anything elsewhere); table (contiguous int64 [R, 8]) row r becomes {label, area, y0, x0, y1, x1, sum_y,
+ * sum_x} -- the root's index, the pixel count, the inclusive bounding box and the coordinate sums -- of the component
+ * of rank r.  Rows no root names are left as they were; a rank outside 0 .. R - 1 is skipped.  int64 atomics (add,
+ * min, max): the result does not depend on the order of arrival. */
+int fg_regions_table(const int* labels, const int* rank, int H, int W, long long* table, int R, hipStream_t stream);
+/* One step of the sieve: writes the whole fp32 0/1 mask [H, W] from a labels plane and its statistics.
+ *   FG_REGIONS_REMOVE (labels of the flood class): mask = 1 on the components with area >= min_area, 0 elsewhere;
+ *   FG_REGIONS_FILL (labels of the dry class): mask = 0 on the dry components that touch the border or have
+ *   area >= min_area, 1 elsewhere (the flood pixels and the filled holes).
+ * counts[0] = the components changed, counts[1] = the pixels changed (device, 8-byte aligned).  min_area <= 1
+ * (REMOVE) or <= 0 (FILL) changes nothing: the mask is the labelled class or its complement, and area / border are
+ * not read and may be null. */
+enum { FG_REGIONS_REMOVE = 0, FG_REGIONS_FILL = 1 };
+int fg_regions_apply(const int* labels, const int* area, const int* border, int H, int W, int mode, int min_area,
+                     float* mask, unsigned long long* counts, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------- */
 /* tile data path                                                    */
 /* ---------------------------------------------------------------------------------------- */
 /* Host-side baseline TIFF decode, replacing tifffile.imread (models/data.py:64-68) for the files
