@@ -9,7 +9,9 @@ evaluation path (segmentation U-Net, device metrics: floodgan.evaluate); torch.l
 floodgan.custom_ops; pictures of predictions, attention and flood masks as PNG files
 (floodgan.render, floodgan.png: converted and composed on the device, encoded on the host); whole scenes
 through a generator in overlapping windows blended on the device (floodgan.scene); the flood regions of a scene --
-connected components, minimum-mapping-unit sieve, region table -- on the device (floodgan.regions).
+connected components, minimum-mapping-unit sieve, region table -- on the device (floodgan.regions); the flood depth
+of a scene from its mask and elevation -- exact nearest-shore transform, depth plane, per-region depth table -- on the
+device (floodgan.depth).
 """
 from ._lib import load as load_library  # noqa: F401
 from .model_architectures import (AttentionGANBlock, AttentionGANDiscriminator,  # noqa: F401
@@ -22,6 +24,8 @@ from .png import read_png, write_png  # noqa: F401
 from .render import Canvas, colormap_lut, save_image, save_sheet, sheet_layout  # noqa: F401
 from .scene import Mosaic, predict_scene, window_grid  # noqa: F401
 from .regions import flood_regions, label_regions, write_regions_csv  # noqa: F401
+from .depth import flood_depth, nearest_seed  # noqa: F401
+from .data import load_scene_elevation  # noqa: F401
 
 __all__ = ["PairedAttentionGenerator", "PairedAttentionBlock", "PairedAttentionDiscriminator",
            "AttentionGANGenerator", "AttentionGANBlock", "AttentionGANDiscriminator",
@@ -29,4 +33,4 @@ __all__ = ["PairedAttentionGenerator", "PairedAttentionBlock", "PairedAttentionD
            "Pix2PixGenerator", "Pix2PixBlock", "Pix2PixDiscriminator", "UNet", "FloodMaskLoss", "load_library", "LPIPS",
            "load_lpips_weights", "Canvas", "colormap_lut", "save_image", "save_sheet", "sheet_layout", "write_png",
            "read_png", "compare_output_images", "Mosaic", "predict_scene", "window_grid", "flood_regions",
-           "label_regions", "write_regions_csv"]
+           "label_regions", "write_regions_csv", "nearest_seed", "flood_depth", "load_scene_elevation"]

@@ -351,6 +351,22 @@ def load_scene(path, topography, device="cuda"):
     return out
 
 
+ELEVATION_CHANNEL, ELEVATION_SCALE = 3, 100.0
+
+
+def load_scene_elevation(path, device="cuda"):
+    """The elevation plane of a scene for floodgan.depth.flood_depth: channel 3 of the 9-channel input stack TIFF at
+    `path`, raw (before Normalize), times 100 in fp32.  The stack stores the DEM as (elevation - min) / 100
+    (pre_processing/data_pre_processing.py:198-205, render_DEM), so the result is metres above the scene's lowest
+    point.  Any other channel count raises ValueError.  Returns fp32 [H, W] on the device."""
+    raw = read_tile(path)
+    if raw.shape[2] != 9:
+        raise ValueError(f"load_scene_elevation: {path} has {raw.shape[2]} channels; the elevation is channel "
+                         f"{ELEVATION_CHANNEL} of the 9-channel input stack")
+    plane = np.ascontiguousarray(raw[:, :, ELEVATION_CHANNEL]) * np.float32(ELEVATION_SCALE)
+    return torch.from_numpy(plane).to(torch.device(device))
+
+
 # ------------------------------------------------------------------------------------------ dataset
 
 class FloodDataset:

@@ -502,7 +502,8 @@ class Model:
         return written
 
     def predict_scene(self, input_path, tile=None, overlap=64, batch=8, seg_model_path=None, batch_stats=False,
-                      out_dir=None, min_region=None, min_hole=None, connectivity=8):
+                      out_dir=None, min_region=None, min_hole=None, connectivity=8, depth=False, pixel_area=1.0,
+                      depth_vmax=None):
         """Not in the reference: the predicted post-flood picture of a whole pre-flood scene, a TIFF of any size that
         need not be a dataset tile (floodgan.data.load_scene, floodgan.scene.predict_scene: overlapping windows
         through the generator -- pre_to_post for the cycle models -- blended on the device).  tile=None: the size the
@@ -513,11 +514,17 @@ class Model:
         need seg_model_path) the mask is sieved (floodgan.regions: flood components below min_region pixels removed,
         enclosed holes below min_hole filled, `connectivity` 8 or 4 for the flood class): {name}_floodMask.png is then
         the sieved mask, {name}_floodRegions.csv beside it lists the regions, and the returned dict gains "regions"
-        (the CSV's path) and "region_count".  Out of scope: attention-mask mosaics, reflect-padding of scenes smaller
+        (the CSV's path) and "region_count".  With depth=True (it needs seg_model_path and a 9-channel file, whose
+        channel 3 is the elevation: floodgan.data.load_scene_elevation) the flood depth of the mask
+        (floodgan.depth.flood_depth with `pixel_area`) is written as {name}_floodDepth.png -- the "attention"
+        rendering of clamp(depth / vmax, 0, 1), vmax = depth_vmax, or the scene's maximum depth, or 1 when that is
+        0 --, {name}_floodMask.png and {name}_floodRegions.csv are written as with the minima (off unless given),
+        the CSV with the depth columns, and the returned dict gains "flood_depth" (the picture's path), "max_depth",
+        "mean_depth" and "volume".  Out of scope: attention-mask mosaics, reflect-padding of scenes smaller
         than a window, GeoTIFF output."""
         import os
 
-        from .data import load_scene
+        from .data import load_scene, load_scene_elevation
         from .render import save_image
         from .scene import predict_scene, scene_name
         if out_dir is None:
@@ -527,11 +534,18 @@ class Model:
             out_dir = f"{self.data_path}/images"
         if tile is None:
             tile = self.resize if self.resize else 512
+        elevation = None
+        if depth:
+            if seg_model_path is None:
+                raise ValueError("predict_scene: depth=True gives the depth of the flood mask and needs seg_model_path")
+            if depth_vmax is not None and not depth_vmax > 0:
+                raise ValueError(f"predict_scene: depth_vmax {depth_vmax!r} must be positive")
+            elevation = load_scene_elevation(input_path, self.device)
         x = load_scene(input_path, self.topography, self.device)
         generator = self.pre_to_post_generator if self.model_is_cycle else self.generator
         res = predict_scene(generator, x, tile=tile, overlap=overlap, batch=batch, seg_model=seg_model_path,
                             batch_stats=batch_stats, min_region=min_region, min_hole=min_hole,
-                            connectivity=connectivity)
+                            connectivity=connectivity, elevation=elevation, pixel_area=pixel_area)
         os.makedirs(out_dir, exist_ok=True)
         name = scene_name(input_path)
         written = {"prediction": save_image(f"{out_dir}/{name}_prediction.png", res["output"], "rgb"),
@@ -539,8 +553,17 @@ class Model:
         if "flood_mask" in res:
             from .regions import write_regions_csv
             written["flood_mask"] = save_image(f"{out_dir}/{name}_floodMask.png", res["flood_mask"], "mask_true")
-            written["regions"] = write_regions_csv(f"{out_dir}/{name}_floodRegions.csv", res["regions"])
+            written["regions"] = write_regions_csv(f"{out_dir}/{name}_floodRegions.csv", res["regions"],
+                                                   res.get("depth"))
             written["region_count"] = res["regions"]["count"]
+            if depth:
+                vmax = depth_vmax if depth_vmax is not None else (res["depth"]["max_depth"] or 1.0)
+                # (a tensor divisor: one correctly rounded fp32 division per pixel, not a product with 1 / vmax)
+                unit = torch.clamp(res["flood_depth"] / torch.tensor(float(vmax), dtype=torch.float32,
+                                                                      device=res["flood_depth"].device), 0.0, 1.0)
+                written["flood_depth"] = save_image(f"{out_dir}/{name}_floodDepth.png", unit, "attention")
+                for key in ("max_depth", "mean_depth", "volume"):
+                    written[key] = res["depth"][key]
         elif "flood_logits" in res:
             written["flood_mask"] = save_image(f"{out_dir}/{name}_floodMask.png", res["flood_logits"], "mask_logits")
         if self.verbose:

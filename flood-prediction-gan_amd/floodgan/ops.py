@@ -1244,3 +1244,76 @@ def regions_apply(labels, area, border, mode, min_area, mask, counts):
     wrote(mask)
     L.check(_lib().fg_regions_apply(L.ptr(labels), L.ptr(area), L.ptr(border), H, W, REGION_MODES[mode], int(min_area),
                                     L.ptr(mask), L.ptr(counts), L.stream_handle()), "regions_apply")
+
+
+# ------------------------------------------------------------------------------------------ flood depth (distance.hip)
+
+MAX_SEED_SIDE = 32768           # fg_nearest_seed: 2 * 32767^2 still fits the int32 squared distance
+
+
+def _float_plane(t, H, W, what):
+    L.require_device(t, what)
+    if t.numel() != H * W or tuple(t.shape[-2:]) != (H, W) or not t.is_contiguous():
+        raise RuntimeError(f"floodgan depth: {what} is a contiguous fp32 [{H}, {W}] device tensor (got "
+                           f"{tuple(t.shape)})")
+    return t
+
+
+def nearest_seed(src, kind, target, nearest, dist2=None):
+    """fg_nearest_seed: nearest (int32 [H, W]) = the index of the nearest pixel of class `target` of channel 0 of src
+    ([1, C, H, W], any strides), ties to the smallest index, dist2 (int32 [H, W] or None) its squared distance; -1
+    in both without a seed.  The scratch (column plane and seed bits) is allocated here, per call."""
+    _, _, H, W = src.shape
+    L.require_device(src, "seed source")
+    _int_plane(nearest, H, W, "the nearest plane")
+    if dist2 is not None:
+        _int_plane(dist2, H, W, "the squared-distance plane")
+    nbytes = int(_lib().fg_nearest_seed_scratch_bytes(H, W))
+    if nbytes <= 0:
+        raise RuntimeError(f"floodgan depth: a scene of {H} x {W}: each side must be 1 .. {MAX_SEED_SIDE}")
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=src.device)
+    L.check(_lib().fg_nearest_seed(sview(src), H, W, REGION_KINDS[kind], int(bool(target)), L.ptr(nearest),
+                                   L.ptr(dist2), L.ptr(scratch), L.stream_handle()), "nearest_seed")
+    return nearest, dist2
+
+
+def shore(mask, out):
+    """fg_shore: out (fp32 [H, W] or [1, 1, H, W]) = 1 on the flood pixels of the 0 / 1 mask with a dry 4-neighbour
+    inside the scene, else 0"""
+    H, W = int(mask.shape[-2]), int(mask.shape[-1])
+    _float_plane(mask, H, W, "the mask")
+    _float_plane(out, H, W, "the shore plane")
+    wrote(out)
+    L.check(_lib().fg_shore(L.ptr(mask), H, W, L.ptr(out), L.stream_handle()), "shore")
+    return out
+
+
+def flood_depth(mask, elevation, nearest, depth):
+    """fg_flood_depth: depth = max(elevation[nearest] - elevation, 0) on the flood pixels of mask, 0 elsewhere"""
+    H, W = nearest.shape
+    _float_plane(mask, H, W, "the mask")
+    _float_plane(elevation, H, W, "the elevation")
+    _int_plane(nearest, H, W, "the nearest plane")
+    _float_plane(depth, H, W, "the depth plane")
+    wrote(depth)
+    L.check(_lib().fg_flood_depth(L.ptr(mask), L.ptr(elevation), L.ptr(nearest), H, W, L.ptr(depth),
+                                  L.stream_handle()), "flood_depth")
+    return depth
+
+
+def depth_table(labels, rank, depth, table):
+    """fg_depth_table: table (int64 [R, 3]) = {wet_area, depth_sum_q, depth_max_q} per region of the labels / rank
+    planes; both None: the whole scene as one region (R = 1)"""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    _float_plane(depth, H, W, "the depth plane")
+    if (labels is None) != (rank is None):
+        raise RuntimeError("floodgan depth: labels and rank plane come together")
+    if labels is not None:
+        _int_plane(labels, H, W, "the labels plane")
+        _int_plane(rank, H, W, "the rank plane")
+    if not (table.is_cuda and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 3
+            and table.is_contiguous()):
+        raise RuntimeError("floodgan depth: the table is a contiguous int64 [R, 3] device tensor")
+    L.check(_lib().fg_depth_table(L.ptr(labels), L.ptr(rank), L.ptr(depth), H, W, L.ptr(table), table.shape[0],
+                                  L.stream_handle()), "depth_table")
+    return table

@@ -36,7 +36,7 @@ COLUMNS = ("label", "area", "y0", "x0", "y1", "x1", "sum_y", "sum_x")
 MAX_PIXELS = 2 ** 31 - 1
 
 
-def _check(src, kind, min_region, min_hole, connectivity):
+def check_source(src, kind, min_region=1, min_hole=0, connectivity=8):
     """the option errors, before any launch; returns the [1, C, H, W] view the kernels read"""
     if kind not in ops.REGION_KINDS:
         raise ValueError(f"regions: kind must be one of {sorted(ops.REGION_KINDS)} (got {kind!r})")
@@ -69,7 +69,7 @@ def label_regions(src, kind="logit", target=True, connectivity=8):
     """int32 [H, W] device tensor: the canonical labels of the flood class (target=True) or of the dry class
     (target=False, labelled with the complementary connectivity) of src -- [H, W], [1, 1, H, W], channel 0 of
     [1, C, H, W] or of an NHWC Buf -- and -1 on the other class (module docstring)."""
-    return _label(_check(src, kind, 1, 0, connectivity), kind, target, connectivity)
+    return _label(check_source(src, kind, 1, 0, connectivity), kind, target, connectivity)
 
 
 def region_table(labels):
@@ -98,7 +98,7 @@ def flood_regions(src, kind="logit", min_region=1, min_hole=0, connectivity=8, t
       "removed", "filled"   the flood components the sieve removed and the holes it filled
       "flood_fraction"  the share of flood pixels of the final mask."""
     min_region, min_hole = int(min_region), int(min_hole)
-    view = _check(src, kind, min_region, min_hole, connectivity)
+    view = check_source(src, kind, min_region, min_hole, connectivity)
     _, _, H, W = view.shape
     dev = view.device
     cap = lambda v: min(v, MAX_PIXELS)                                     # noqa: E731  (an area never exceeds it)
@@ -136,15 +136,29 @@ def flood_regions(src, kind="logit", min_region=1, min_hole=0, connectivity=8, t
     return res
 
 
-def write_regions_csv(path, regions):
+DEPTH_COLUMNS = ("wet_area", "mean_depth", "max_depth", "volume")
+
+
+def write_regions_csv(path, regions, depth=None):
     """One header line (COLUMNS, then centroid_y, centroid_x) and one line per region of a flood_regions result;
-    integers as integers, the centroids by repr (they read back to the same fp64).  Returns path."""
+    integers as integers, the centroids by repr (they read back to the same fp64).  With `depth` (a
+    floodgan.depth.flood_depth result computed with these regions) the lines gain DEPTH_COLUMNS: wet_area as an
+    integer, the others by repr.  Returns path."""
     tab, cen = regions["table"], regions["centroids"]
     if tab is None:
         raise ValueError("write_regions_csv: the regions were computed with table=False")
+    head, dtab = COLUMNS + ("centroid_y", "centroid_x"), None
+    if depth is not None:
+        dtab = depth.get("table")
+        if dtab is None or len(dtab["wet_area"]) != len(tab["label"]):
+            raise ValueError("write_regions_csv: the depth result holds no table of these regions (flood_depth with "
+                             "regions=)")
+        head = head + DEPTH_COLUMNS
     with open(path, "w") as f:
-        f.write(",".join(COLUMNS + ("centroid_y", "centroid_x")) + "\n")
+        f.write(",".join(head) + "\n")
         for r in range(len(tab["label"])):
-            f.write(",".join([str(int(tab[c][r])) for c in COLUMNS] + [repr(float(cen[r, 0])), repr(float(cen[r, 1]))])
-                    + "\n")
+            cells = [str(int(tab[c][r])) for c in COLUMNS] + [repr(float(cen[r, 0])), repr(float(cen[r, 1]))]
+            if dtab is not None:
+                cells += [str(int(dtab["wet_area"][r]))] + [repr(float(dtab[c][r])) for c in DEPTH_COLUMNS[1:]]
+            f.write(",".join(cells) + "\n")
     return path

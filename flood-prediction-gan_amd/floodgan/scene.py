@@ -155,7 +155,7 @@ def _flood_logits(unet, images, batch_stats):
 
 
 def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, batch_stats=False, min_region=None,
-                  min_hole=None, connectivity=8):
+                  min_hole=None, connectivity=8, elevation=None, pixel_area=1.0):
     """A device scene x [1, C, H, W] in [-1, 1] through `generator` in windows of tile x tile pixels, `batch` at a
     time (the last batch may be smaller), blended by Mosaic.  Runs under torch.no_grad() with torch.manual_seed(47)
     before each generator call, as the package's picture paths do; the generator runs in the mode it is in.
@@ -171,11 +171,26 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
     logits (floodgan.regions.flood_regions with the minima -- None is "off" -- and `connectivity`): the result gains
     "flood_mask" (fp32 [1, 1, H, W] of 0 / 1, sieved), "regions" (flood_regions' dict without its mask) and
     "flood_fraction_sieved"; "flood_logits" and "flood_fraction" are what they are without the minima.
+    elevation (fp32 [H, W] or [1, 1, H, W] on the scene's device, with seg_model; ValueError without, or on another
+    shape or device, before any launch): the depth product of the flood mask (floodgan.depth.flood_depth with the
+    regions and `pixel_area`) -- of the sieved mask when minima are given, else of the plain decision, which the
+    result then also carries as "flood_mask" and "regions" (flood_regions with the minima off).  The result gains
+    "flood_depth" (fp32 [1, 1, H, W]) and "depth" (flood_depth's dict without its plane).
     Out of scope: attention-mask mosaics, reflect-padding of scenes smaller than a window, GeoTIFF output."""
+    if elevation is not None and seg_model is None:
+        raise ValueError("predict_scene: elevation gives the depth of the flood mask and needs seg_model")
     require_device(x, "scene")
     if x.dim() != 4 or x.shape[0] != 1:
         raise ValueError(f"predict_scene: a [1, C, H, W] scene (got {tuple(x.shape)})")
     H, W = int(x.shape[2]), int(x.shape[3])
+    if elevation is not None:
+        if connectivity not in (4, 8):
+            raise ValueError(f"predict_scene: connectivity {connectivity!r} must be 4 or 8")
+        if not (torch.is_tensor(elevation) and elevation.dtype == torch.float32
+                and tuple(elevation.shape) in ((H, W), (1, 1, H, W)) and elevation.device == x.device):
+            raise ValueError(f"predict_scene: the elevation must be a float32 [{H}, {W}] or [1, 1, {H}, {W}] tensor on "
+                             f"{x.device} (got {getattr(elevation, 'dtype', type(elevation))} "
+                             f"{tuple(getattr(elevation, 'shape', ()))} on {getattr(elevation, 'device', 'the host')})")
     if batch < 1:
         raise ValueError(f"predict_scene: batch {batch} must be positive")
     whole = tile is None
@@ -227,6 +242,16 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
                 res["flood_mask"] = regions.pop("mask")
                 res["regions"] = regions
                 res["flood_fraction_sieved"] = regions["flood_fraction"]
+            if elevation is not None:
+                from .depth import flood_depth
+                if not sieve:
+                    from .regions import flood_regions
+                    regions = flood_regions(logits, "logit", 1, 0, connectivity)
+                    res["flood_mask"] = regions.pop("mask")
+                    res["regions"] = regions
+                depth = flood_depth(res["flood_mask"], elevation, res["regions"], pixel_area)
+                res["flood_depth"] = depth.pop("depth")
+                res["depth"] = depth
     return res
 
 

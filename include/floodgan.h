@@ -774,6 +774,47 @@ int fg_regions_apply(const int* labels, const int* area, const int* border, int 
                      float* mask, unsigned long long* counts, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------- */
+/* flood depth: nearest-seed transform, shore, depth, depth table (not in the reference) */
+/* ---------------------------------------------------------------------------------------- */
+/* Pixel indices are i = y * W + x as for the regions; the transform and the table are integer-exact.  Every entry
+ * fails with FG_ERR_INVALID and writes nothing on a null pointer it needs, a size that is not positive or too large,
+ * a misaligned pointer or an unknown kind or target.  Indices the kernels read from device memory (column results,
+ * nearest indices, labels, ranks) are checked against the plane or table they index before use.
+ *
+ * fg_nearest_seed: the exact Euclidean feature transform.  A pixel of channel 0 of src (a strided view, as
+ * fg_regions_label takes it) is a SEED when its class under `kind` (FG_SCALAR_LOGIT / FG_SCALAR_THRESHOLD, the
+ * decisions of fg_regions_label) equals `target` (1 flood, 0 dry).  For every pixel p = (y, x): dist2[p] = the
+ * minimum over the seeds s = (y', x') of (y - y')^2 + (x - x')^2, nearest[p] = the index y' W + x' of the seed that
+ * attains it and, among several, the one with the SMALLEST index: the outputs are a function of the seed plane alone.
+ * A seed names itself with dist2 0; a scene without a seed gets -1 in both planes.  nearest, dist2: contiguous int32
+ * [H, W]; dist2 may be null.  H and W are at most 32768, so that the largest squared distance, 2 * 32767^2, fits
+ * int32.  scratch: fg_nearest_seed_scratch_bytes(H, W) bytes of device memory, 8-byte aligned, the caller's (the
+ * library allocates nothing): the column pass's plane (int32 [H, W]: per pixel the nearest seed row of its column)
+ * and the seed bits (one 64-bit word per 64 rows of a column); their contents after the call are unspecified.  Three
+ * launches whatever the data: seed bits, column pass, row pass (an outward search over the columns, staged in LDS
+ * in chunks of 256); no atomics, no workgroup waits for another.  fg_nearest_seed_scratch_bytes returns 0 for sizes
+ * fg_nearest_seed refuses. */
+long long fg_nearest_seed_scratch_bytes(int H, int W);
+int fg_nearest_seed(fg_sview src, int H, int W, int kind, int target, int* nearest, int* dist2, void* scratch,
+                    hipStream_t stream);
+/* shore[i] = 1 where mask[i] > 0.5 and at least one 4-neighbour INSIDE the scene is not (a flood pixel on the scene's
+ * edge is not shore by the edge alone), else 0.  mask, shore: contiguous fp32 [H, W], distinct. */
+int fg_shore(const float* mask, int H, int W, float* shore, hipStream_t stream);
+/* depth[p] = max(elev[nearest[p]] - elev[p], 0) -- one fp32 subtraction, d > 0 ? d : 0, so a negative or NaN
+ * difference gives 0 -- where mask[p] > 0.5 and nearest[p] names a pixel of the scene; 0 elsewhere (dry pixels, a
+ * scene without a shore).  All planes contiguous [H, W]; depth must not be elev. */
+int fg_flood_depth(const float* mask, const float* elev, const int* nearest, int H, int W, float* depth,
+                   hipStream_t stream);
+/* The depth table, with the labels / rank protocol of fg_regions_table: table (contiguous int64 [R, 3]) row r becomes
+ * {wet_area, depth_sum_q, depth_max_q} of the component of rank r, over q(p) = (long long) rintf(fminf(depth[p],
+ * 1048576) * 1024) (fixed point, quantum 2^-10; the scaling is exact in fp32, the rounding half-to-even): the number
+ * of its pixels with q > 0, their sum and their maximum.  The whole table is cleared first, so a row no root names is
+ * {0, 0, 0}.  labels and rank both null: the scene is one region, R must be 1.  int64 atomic add and max only: the
+ * result does not depend on the order of arrival. */
+int fg_depth_table(const int* labels, const int* rank, const float* depth, int H, int W, long long* table, int R,
+                   hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------- */
 /* tile data path                                                    */
 /* ---------------------------------------------------------------------------------------- */
 /* Host-side baseline TIFF decode, replacing tifffile.imread (models/data.py:64-68) for the files
