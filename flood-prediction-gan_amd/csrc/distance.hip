@@ -22,47 +22,30 @@
 // Every loop is counted: by the rows of a band (64), the bands (ceil(H / 64)), the rings (ceil(W / CH) + 1) or the
 // columns of a ring (CH).
 //
-// fg_depth_table follows regions.hip's statistics launch: a lane owns a run of RUN pixels of a row and merges its
-// pixels of equal root into one update, the wave merges what is left by root for MERGE_ROUNDS roots, the rest goes out
-// lane by lane; int64 add and max only, so the table does not depend on the order of arrival.
-#include <limits.h>
-
-#include "fg_common.hpp"
+// fg_depth_table is a policy of scene_common.hpp's accumulation kernel, which holds the loop and its reasons: int64
+// add and max only.
+#include "scene_common.hpp"
 
 namespace {
 
-constexpr int NT = 256;
+using namespace fg::scene;
+
 constexpr int BAND = 64;                            // rows per band word
 constexpr int CH = 256;                             // columns per row-pass segment and per staged chunk (= NT)
-constexpr int RUN = 4;                              // pixels of a row a lane of the table kernel owns
-constexpr int MERGE_ROUNDS = 4;                     // roots per wave whose updates are merged before the atomics
 constexpr int MAX_SIDE = 32768;                     // 2 * 32767^2 < 2^31: every squared distance fits int32
 constexpr float Q_CAP = 1048576.0f, Q_SCALE = 1024.0f;
 
-#define FG_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
 typedef unsigned long long u64;
 
-struct Seeds {
-    const float* p;
-    long long sy, sx;
-    int kind, target;
-    __device__ __forceinline__ bool seed(int y, int x) const {
-        const float v = p[y * sy + x * sx];
-        const bool wet = kind == FG_SCALAR_LOGIT ? fg::flood(v) : v > 0.5f;
-        return wet == (target != 0);
-    }
-};
-
 // bits[b * W + x]: bit r set when pixel (64 b + r, x) is a seed (rows >= H are never set)
-__global__ void __launch_bounds__(NT) seed_bits_kernel(Seeds s, int H, int W, int nb, u64* bits) {
+__global__ void __launch_bounds__(NT) seed_bits_kernel(ClassPlane s, int H, int W, int nb, u64* bits) {
     const long long total = (long long)nb * W;
     for (long long i = blockIdx.x * (long long)NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
         const int b = (int)(i / W), x = (int)(i % W), y0 = b * BAND;
         u64 w = 0;
 #pragma unroll 8
         for (int r = 0; r < BAND; ++r)
-            if (y0 + r < H && s.seed(y0 + r, x)) w |= 1ull << r;
+            if (y0 + r < H && s.member(y0 + r, x)) w |= 1ull << r;
         bits[i] = w;
     }
 }
@@ -192,98 +175,46 @@ __global__ void __launch_bounds__(NT) depth_kernel(const float* mask, const floa
     }
 }
 
-// ---- the depth table
+// ---- the depth table: a policy of accumulate_kernel
 
-struct DAcc {
-    int root, wet;
-    long long sum, mx;
-};
-
-__device__ __forceinline__ DAcc empty_dacc() { return DAcc{-1, 0, 0, 0}; }
-
-struct DSink {
+// table[rank[root]] = {wet_area, depth_sum_q, depth_max_q} over the pixels whose depth rounds to at least one quantum;
+// the quantum is a pixel's weight, so a shallower pixel is left out before its root is looked at
+struct DepthTable {
+    struct Acc {
+        int root, n;
+        long long sum, mx;
+    };
     int H, W;
-    const int* rank;            // plane indexed by root; null with the whole scene as one region
+    const int* labels;          // null with rank: the whole scene as one region, row 0
+    const int* rank;            // plane indexed by root
+    const float* depth;
     long long* table;           // [R, 3]
     int R;
-};
-
-__device__ __forceinline__ void emit(const DSink& k, const DAcc& a) {
-    if (a.wet <= 0 || (unsigned)a.root >= (unsigned)(k.H * k.W)) return;
-    const int r = k.rank ? k.rank[a.root] : 0;
-    if ((unsigned)r >= (unsigned)k.R) return;
-    long long* row = k.table + 3ll * r;
-    __hip_atomic_fetch_add(row + 0, (long long)a.wet, FG_RLX_AGENT);
-    __hip_atomic_fetch_add(row + 1, a.sum, FG_RLX_AGENT);
-    __hip_atomic_fetch_max(row + 2, a.mx, FG_RLX_AGENT);
-}
-
-__device__ __forceinline__ long long quantum(float d) { return (long long)rintf(fminf(d, Q_CAP) * Q_SCALE); }
-
-__global__ void __launch_bounds__(NT) depth_table_kernel(const int* labels, const float* depth, DSink k, int runs) {
-    const long long total = (long long)k.H * runs;
-    // the bound is the same for every lane of a block: the wave-wide steps below see whole waves
-    for (long long i0 = blockIdx.x * (long long)NT; i0 < total; i0 += (long long)gridDim.x * NT) {
-        const long long i = i0 + threadIdx.x;
-        DAcc a = empty_dacc();
-        if (i < total) {
-            const int y = (int)(i / runs), xq = RUN * (int)(i % runs);
-            const long long at = (long long)y * k.W + xq;
-#pragma unroll
-            for (int e = 0; e < RUN; ++e) {
-                if (xq + e >= k.W) break;
-                const int l = labels ? labels[at + e] : 0;
-                if (l < 0) continue;
-                const long long q = quantum(depth[at + e]);
-                if (q <= 0) continue;
-                if (l != a.root) {
-                    emit(k, a);
-                    a = empty_dacc();
-                    a.root = l;
-                }
-                a.wet += 1;
-                a.sum += q;
-                a.mx = q > a.mx ? q : a.mx;
-            }
-        }
-        // variant: `pending` loses at least its lowest set bit every round (the leader is in its own group)
-        const int lane = threadIdx.x & 63;
-        u64 pending = __ballot(a.wet > 0);
-        for (int round = 0; pending != 0 && round < MERGE_ROUNDS; ++round) {
-            const int leader = __ffsll((long long)pending) - 1;
-            const int r0 = __shfl(a.root, leader);
-            const bool mine = a.wet > 0 && a.root == r0;
-            const u64 group = __ballot(mine);
-            if (__popcll(group) == 1) {
-                if (mine) emit(k, a);
-            } else {
-                DAcc g = mine ? a : empty_dacc();
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    g.wet += __shfl_xor(g.wet, d);
-                    g.sum += __shfl_xor(g.sum, d);
-                    const long long o = __shfl_xor(g.mx, d);
-                    g.mx = o > g.mx ? o : g.mx;
-                }
-                g.root = r0;
-                if (lane == leader) emit(k, g);
-            }
-            if (mine) a.wet = 0;
-            pending &= ~group;
-        }
-        emit(k, a);                 // (nothing when a round took it: wet is 0)
+    static __device__ __forceinline__ Acc empty() { return Acc{-1, 0, 0, 0}; }
+    __device__ __forceinline__ long long weight(long long at) const {
+        return (long long)rintf(fminf(depth[at], Q_CAP) * Q_SCALE);
     }
-}
-
-inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-int check_scene(const char* who, int H, int W) {
-    if (H <= 0 || W <= 0) return fg::fail(FG_ERR_INVALID, "%s: sizes must be positive (scene %d x %d)", who, H, W);
-    if ((long long)H * W > INT_MAX)
-        return fg::fail(FG_ERR_INVALID, "%s: a scene of %d x %d = %lld pixels: indices are int32, H * W must be below "
-                        "2^31", who, H, W, (long long)H * W);
-    return 0;
-}
+    __device__ __forceinline__ void add(Acc& a, int, int, long long q) const {
+        a.n += 1;
+        a.sum += q;
+        a.mx = max(a.mx, q);
+    }
+    static __device__ __forceinline__ void merge(Acc& g, int d) {
+        g.n += __shfl_xor(g.n, d);
+        g.sum += __shfl_xor(g.sum, d);
+        g.mx = max(g.mx, __shfl_xor(g.mx, d));
+    }
+    // every index that comes out of memory is checked against the plane or the table before it is used
+    __device__ __forceinline__ void emit(const Acc& a) const {
+        if (a.n <= 0 || (unsigned)a.root >= (unsigned)(H * W)) return;
+        const int r = rank ? rank[a.root] : 0;
+        if ((unsigned)r >= (unsigned)R) return;
+        long long* row = table + 3ll * r;
+        __hip_atomic_fetch_add(row + 0, (long long)a.n, FG_RLX_AGENT);
+        __hip_atomic_fetch_add(row + 1, a.sum, FG_RLX_AGENT);
+        __hip_atomic_fetch_max(row + 2, a.mx, FG_RLX_AGENT);
+    }
+};
 
 inline long long col_bytes(int H, int W) { return ((long long)H * W * 4 + 7) / 8 * 8; }
 inline int bands(int H) { return (H + BAND - 1) / BAND; }
@@ -303,17 +234,15 @@ FG_API int fg_nearest_seed(fg_sview src, int H, int W, int kind, int target, int
         return fg::fail(FG_ERR_INVALID, "%s: a scene of %d x %d: each side must be 1 .. %d (squared distances are "
                         "int32)", who, H, W, MAX_SIDE);
     if (int e = check_scene(who, H, W)) return e;
-    if (kind != FG_SCALAR_THRESHOLD && kind != FG_SCALAR_LOGIT)
-        return fg::fail(FG_ERR_INVALID, "%s: kind %d (FG_SCALAR_THRESHOLD or FG_SCALAR_LOGIT)", who, kind);
-    if (target != 0 && target != 1) return fg::fail(FG_ERR_INVALID, "%s: target %d (0 dry, 1 flood)", who, target);
+    if (int e = check_class(who, kind, target)) return e;
     if (!aligned(src.ptr, 4) || !aligned(nearest, 4) || (dist2 && !aligned(dist2, 4)) || !aligned(scratch, 8))
         return fg::fail(FG_ERR_INVALID, "%s: source and planes must be 4-byte, the scratch 8-byte aligned", who);
     int* col = static_cast<int*>(scratch);
     u64* bits = reinterpret_cast<u64*>(static_cast<char*>(scratch) + col_bytes(H, W));
     const int nb = bands(H), segs = (W + CH - 1) / CH;
     const int grid = fg::blocks_for((long long)nb * W, NT, 1 << 16);
-    hipLaunchKernelGGL(seed_bits_kernel, dim3(grid), dim3(NT), 0, stream, Seeds{src.ptr, src.sy, src.sx, kind, target},
-                       H, W, nb, bits);
+    hipLaunchKernelGGL(seed_bits_kernel, dim3(grid), dim3(NT), 0, stream,
+                       ClassPlane{src.ptr, src.sy, src.sx, kind, target}, H, W, nb, bits);
     hipLaunchKernelGGL(column_kernel, dim3(grid), dim3(NT), 0, stream, bits, H, W, nb, col);
     hipLaunchKernelGGL(row_kernel, dim3((unsigned)((long long)H * segs)), dim3(NT), 0, stream, col, H, W, segs, nearest,
                        dist2);
@@ -360,8 +289,6 @@ FG_API int fg_depth_table(const int* labels, const int* rank, const float* depth
         return fg::fail(FG_ERR_INVALID, "%s: planes must be 4-byte, the table 8-byte aligned", who);
     if (hipMemsetAsync(table, 0, sizeof(long long) * 3 * (size_t)R, stream) != hipSuccess)
         return fg::fail(FG_ERR_INVALID, "%s: clearing the table failed", who);
-    const int runs = (W + RUN - 1) / RUN;
-    hipLaunchKernelGGL(depth_table_kernel, dim3(fg::blocks_for((long long)H * runs, NT, 4096)), dim3(NT), 0, stream,
-                       labels, depth, DSink{H, W, rank, table, R}, runs);
+    launch_accumulate(DepthTable{H, W, labels, rank, depth, table, R}, stream);
     return fg::launched("depth_table");
 }

@@ -18,24 +18,17 @@
 // need.  The kernel boundaries publish each phase to the next; no workgroup ever waits for another.
 // Every loop below ends by a strictly decreasing non-negative integer; each states it.
 //
-// Statistics (fg_regions_stats, fg_regions_table) use integer atomics only (int32 areas, int64 sums, min / max for
-// the boxes), so the results do not depend on the order of arrival.  A lane owns a run of RUN pixels of a row and
-// merges its pixels of equal root into one update; the updates a wave is left with at the end of its runs are merged
-// across the wave by root, for the first MERGE_ROUNDS roots it holds (the interior of a large region, or the border of
-// two: one or two sets of atomics per 256 pixels instead of up to 64).  The table launch's time is the number of its
-// atomic instructions (seven per update, onto one 64-byte row per region), which is what the merging is for.
-#include <limits.h>
-
-#include "fg_common.hpp"
+// Statistics (fg_regions_stats, fg_regions_table) are two policies of scene_common.hpp's accumulation kernel, which
+// holds the loop and its reasons: int32 areas and flags, int64 sums, min / max for the boxes.  An update of the table
+// is seven atomic instructions onto one 64-byte row per region.
+#include "scene_common.hpp"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int TW = 64, TH = 16, TPX = TW * TH;      // a wave reads one 256-byte tile row of a unit-stride source
-constexpr int RUN = 4;                              // pixels of a row a lane of the statistics kernels owns
-constexpr int MERGE_ROUNDS = 4;                     // roots per wave whose updates are merged before the atomics
+using namespace fg::scene;
 
-#define FG_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+constexpr int TW = 64, TH = 16, TPX = TW * TH;      // a wave reads one 256-byte tile row of a unit-stride source
+
 #define FG_RLX_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
 
 // ---- union-find on the global parent plane (agent scope) and on a tile in LDS (workgroup scope)
@@ -77,18 +70,8 @@ __device__ __forceinline__ void unite(const F& f, int a, int b) {
     }
 }
 
-struct Mask {
-    const float* p;
-    long long sy, sx;
-    int kind, target;
-    __device__ __forceinline__ bool member(int y, int x) const {
-        const float v = p[y * sy + x * sx];
-        const bool wet = kind == FG_SCALAR_LOGIT ? fg::flood(v) : v > 0.5f;
-        return wet == (target != 0);
-    }
-};
-
-__global__ void __launch_bounds__(NT) label_tiles_kernel(Mask m, int H, int W, int tiles_x, int conn8, int* labels) {
+__global__ void __launch_bounds__(NT) label_tiles_kernel(ClassPlane m, int H, int W, int tiles_x, int conn8,
+                                                         int* labels) {
     __shared__ int lab[TPX];
     const TileForest f{lab};
     const int ty0 = (int)(blockIdx.x / tiles_x) * TH, tx0 = (int)(blockIdx.x % tiles_x) * TW;
@@ -165,41 +148,74 @@ __global__ void __launch_bounds__(NT) compress_kernel(int* labels, long long tot
     }
 }
 
-// ---- statistics
+// ---- statistics: two policies of accumulate_kernel.  Every index that comes out of memory is checked against the
+// plane or the table before it is used.
 
-struct Acc {
-    int root, cnt, y0, x0, y1, x1;
-    long long sy, sx;
+// area[root]: the pixels of the region; border[root]: 1 when one of them lies in the scene's first or last row or column
+struct AreaPlanes {
+    struct Acc { int root, n, edge; };
+    int H, W;
+    const int* labels;
+    int* area;                  // planes indexed by root
+    int* border;
+    static __device__ __forceinline__ Acc empty() { return Acc{-1, 0, 0}; }
+    __device__ __forceinline__ long long weight(long long) const { return 1; }
+    __device__ __forceinline__ void add(Acc& a, int y, int x, long long) const {
+        a.n += 1;
+        a.edge |= y == 0 || x == 0 || y == H - 1 || x == W - 1;
+    }
+    static __device__ __forceinline__ void merge(Acc& g, int d) {
+        g.n += __shfl_xor(g.n, d);
+        g.edge |= __shfl_xor(g.edge, d);
+    }
+    __device__ __forceinline__ void emit(const Acc& a) const {
+        if (a.n <= 0 || (unsigned)a.root >= (unsigned)(H * W)) return;
+        __hip_atomic_fetch_add(area + a.root, a.n, FG_RLX_AGENT);
+        if (a.edge) __hip_atomic_fetch_or(border + a.root, 1, FG_RLX_AGENT);
+    }
 };
-
-__device__ __forceinline__ Acc empty_acc() { return Acc{-1, 0, INT_MAX, INT_MAX, -1, -1, 0, 0}; }
 
 __device__ __forceinline__ void ll_min(long long* p, long long v) { __hip_atomic_fetch_min(p, v, FG_RLX_AGENT); }
 __device__ __forceinline__ void ll_max(long long* p, long long v) { __hip_atomic_fetch_max(p, v, FG_RLX_AGENT); }
 __device__ __forceinline__ void ll_add(long long* p, long long v) { __hip_atomic_fetch_add(p, v, FG_RLX_AGENT); }
 
-struct Sink {
+// table[rank[root]] = {label, area, y0, x0, y1, x1, sum_y, sum_x}
+struct BoxTable {
+    struct Acc {
+        int root, n, y0, x0, y1, x1;
+        long long sy, sx;
+    };
     int H, W;
-    int* area;                  // planes indexed by root (area mode)
-    int* border;
-    const int* rank;            // plane indexed by root, and the [R, 8] table (table mode)
-    long long* table;
+    const int* labels;
+    const int* rank;            // plane indexed by root
+    long long* table;           // [R, 8]
     int R;
-};
-
-// every index that comes out of memory is checked against the plane or the table before it is used
-template <bool TABLE>
-__device__ __forceinline__ void emit(const Sink& k, const Acc& a) {
-    if (a.cnt <= 0 || (unsigned)a.root >= (unsigned)(k.H * k.W)) return;
-    if (!TABLE) {
-        __hip_atomic_fetch_add(k.area + a.root, a.cnt, FG_RLX_AGENT);
-        if (a.y0 == 0 || a.x0 == 0 || a.y1 == k.H - 1 || a.x1 == k.W - 1)
-            __hip_atomic_fetch_or(k.border + a.root, 1, FG_RLX_AGENT);
-    } else {
-        const int r = k.rank[a.root];
-        if ((unsigned)r >= (unsigned)k.R) return;
-        long long* row = k.table + 8ll * r;
-        ll_add(row + 1, a.cnt);
+    static __device__ __forceinline__ Acc empty() { return Acc{-1, 0, INT_MAX, INT_MAX, -1, -1, 0, 0}; }
+    __device__ __forceinline__ long long weight(long long) const { return 1; }
+    __device__ __forceinline__ void add(Acc& a, int y, int x, long long) const {
+        a.n += 1;
+        a.y0 = min(a.y0, y);
+        a.x0 = min(a.x0, x);
+        a.y1 = max(a.y1, y);
+        a.x1 = max(a.x1, x);
+        a.sy += y;
+        a.sx += x;
+    }
+    static __device__ __forceinline__ void merge(Acc& g, int d) {
+        g.n += __shfl_xor(g.n, d);
+        g.y0 = min(g.y0, __shfl_xor(g.y0, d));
+        g.x0 = min(g.x0, __shfl_xor(g.x0, d));
+        g.y1 = max(g.y1, __shfl_xor(g.y1, d));
+        g.x1 = max(g.x1, __shfl_xor(g.x1, d));
+        g.sy += __shfl_xor(g.sy, d);
+        g.sx += __shfl_xor(g.sx, d);
+    }
+    __device__ __forceinline__ void emit(const Acc& a) const {
+        if (a.n <= 0 || (unsigned)a.root >= (unsigned)(H * W)) return;
+        const int r = rank[a.root];
+        if ((unsigned)r >= (unsigned)R) return;
+        long long* row = table + 8ll * r;
+        ll_add(row + 1, a.n);
         ll_min(row + 2, a.y0);
         ll_min(row + 3, a.x0);
         ll_max(row + 4, a.y1);
@@ -207,83 +223,13 @@ __device__ __forceinline__ void emit(const Sink& k, const Acc& a) {
         ll_add(row + 6, a.sy);
         ll_add(row + 7, a.sx);
     }
-}
-
-template <bool TABLE>
-__global__ void __launch_bounds__(NT) stats_kernel(const int* labels, Sink k, int runs, int vec) {
-    const long long total = (long long)k.H * runs;
-    // the bound is the same for every lane of a block: the wave-wide steps below see whole waves
-    for (long long i0 = blockIdx.x * (long long)NT; i0 < total; i0 += (long long)gridDim.x * NT) {
-        const long long i = i0 + threadIdx.x;
-        Acc a = empty_acc();
-        if (i < total) {
-            const int y = (int)(i / runs), xq = RUN * (int)(i % runs);
-            const int* lp = labels + (long long)y * k.W + xq;
-            int l[RUN];
-            if (vec) {
-                const int4 t = *reinterpret_cast<const int4*>(lp);
-                l[0] = t.x; l[1] = t.y; l[2] = t.z; l[3] = t.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < RUN; ++e) l[e] = xq + e < k.W ? lp[e] : -1;
-            }
-#pragma unroll
-            for (int e = 0; e < RUN; ++e) {
-                if (l[e] < 0) continue;
-                if (l[e] != a.root) {
-                    emit<TABLE>(k, a);
-                    a = empty_acc();
-                    a.root = l[e];
-                    a.y0 = a.y1 = y;
-                    a.x0 = xq + e;
-                }
-                a.cnt += 1;
-                a.x1 = xq + e;
-                a.sy += y;
-                a.sx += xq + e;
-            }
-        }
-        // the updates the wave is left with, merged by root: the first lane that still holds one leads a round, the
-        // lanes of its root join it.  MERGE_ROUNDS rounds cover the roots a wave of a smooth mask meets; what a
-        // speckled one leaves over goes out lane by lane.
-        // variant: `pending` loses at least its lowest set bit every round (the leader is in its own group)
-        const int lane = threadIdx.x & 63;
-        unsigned long long pending = __ballot(a.cnt > 0);
-        for (int round = 0; pending != 0 && round < MERGE_ROUNDS; ++round) {
-            const int leader = __ffsll((long long)pending) - 1;
-            const int r0 = __shfl(a.root, leader);
-            const bool mine = a.cnt > 0 && a.root == r0;
-            const unsigned long long group = __ballot(mine);
-            if (__popcll(group) == 1) {
-                if (mine) emit<TABLE>(k, a);
-            } else {
-                // butterfly over the wave; the lanes outside the group hold the neutral element of each field
-                Acc g = mine ? a : empty_acc();
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    g.cnt += __shfl_xor(g.cnt, d);
-                    g.y0 = min(g.y0, __shfl_xor(g.y0, d));
-                    g.x0 = min(g.x0, __shfl_xor(g.x0, d));
-                    g.y1 = max(g.y1, __shfl_xor(g.y1, d));
-                    g.x1 = max(g.x1, __shfl_xor(g.x1, d));
-                    g.sy += __shfl_xor(g.sy, d);
-                    g.sx += __shfl_xor(g.sx, d);
-                }
-                g.root = r0;
-                if (lane == leader) emit<TABLE>(k, g);
-            }
-            if (mine) a.cnt = 0;
-            pending &= ~group;
-        }
-        emit<TABLE>(k, a);          // (nothing when a round took it: cnt is 0)
-    }
-}
+};
 
 // table[rank[p]] = {p, 0, H, W, -1, -1, 0, 0} at every root p: the neutral row the table launch accumulates into
-__global__ void __launch_bounds__(NT) table_init_kernel(const int* labels, Sink k) {
+__global__ void __launch_bounds__(NT) table_init_kernel(BoxTable k) {
     const long long total = (long long)k.H * k.W;
     for (long long i = blockIdx.x * (long long)NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
-        if (labels[i] != (int)i) continue;
+        if (k.labels[i] != (int)i) continue;
         const int r = k.rank[i];
         if ((unsigned)r >= (unsigned)k.R) continue;
         long long* row = k.table + 8ll * r;
@@ -323,17 +269,6 @@ __global__ void __launch_bounds__(NT) apply_kernel(const int* labels, const int*
     }
 }
 
-inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// 0, or the error code after recording why an H x W scene cannot be indexed by int32
-int check_scene(const char* who, int H, int W) {
-    if (H <= 0 || W <= 0) return fg::fail(FG_ERR_INVALID, "%s: sizes must be positive (scene %d x %d)", who, H, W);
-    if ((long long)H * W > INT_MAX)
-        return fg::fail(FG_ERR_INVALID, "%s: a scene of %d x %d = %lld pixels: labels are int32 pixel indices, H * W "
-                        "must be below 2^31", who, H, W, (long long)H * W);
-    return 0;
-}
-
 }  // namespace
 
 FG_API int fg_regions_label(fg_sview src, int H, int W, int kind, int target, int connectivity, int* labels,
@@ -341,9 +276,7 @@ FG_API int fg_regions_label(fg_sview src, int H, int W, int kind, int target, in
     const char* who = "fg_regions_label";
     if (!src.ptr || !labels) return fg::fail(FG_ERR_INVALID, "%s: null source or labels", who);
     if (int e = check_scene(who, H, W)) return e;
-    if (kind != FG_SCALAR_THRESHOLD && kind != FG_SCALAR_LOGIT)
-        return fg::fail(FG_ERR_INVALID, "%s: kind %d (FG_SCALAR_THRESHOLD or FG_SCALAR_LOGIT)", who, kind);
-    if (target != 0 && target != 1) return fg::fail(FG_ERR_INVALID, "%s: target %d (0 dry, 1 flood)", who, target);
+    if (int e = check_class(who, kind, target)) return e;
     if (connectivity != 4 && connectivity != 8)
         return fg::fail(FG_ERR_INVALID, "%s: connectivity %d (4 or 8)", who, connectivity);
     if (!aligned(src.ptr, 4) || !aligned(labels, 4))
@@ -354,7 +287,7 @@ FG_API int fg_regions_label(fg_sview src, int H, int W, int kind, int target, in
     const int nbh = (H - 1) / TH, nbv = (W - 1) / TW;
     const long long total = (long long)H * W, border = (long long)nbh * W + (long long)nbv * H;
     hipLaunchKernelGGL(label_tiles_kernel, dim3((unsigned)(tiles_x * (long long)tiles_y)), dim3(NT), 0, stream,
-                       Mask{src.ptr, src.sy, src.sx, kind, target}, H, W, tiles_x, conn8, labels);
+                       ClassPlane{src.ptr, src.sy, src.sx, kind, target}, H, W, tiles_x, conn8, labels);
     if (border > 0)
         hipLaunchKernelGGL(merge_borders_kernel, dim3(fg::blocks_for(border, NT, 4096)), dim3(NT), 0, stream, labels,
                            H, W, nbh, nbv, conn8);
@@ -371,10 +304,7 @@ FG_API int fg_regions_stats(const int* labels, int H, int W, int* area, int* bor
     const size_t bytes = sizeof(int) * (size_t)H * W;
     if (hipMemsetAsync(area, 0, bytes, stream) != hipSuccess || hipMemsetAsync(border, 0, bytes, stream) != hipSuccess)
         return fg::fail(FG_ERR_INVALID, "%s: clearing the planes failed", who);
-    const int runs = (W + RUN - 1) / RUN;
-    const int vec = W % RUN == 0 && aligned(labels, 16);
-    hipLaunchKernelGGL(stats_kernel<false>, dim3(fg::blocks_for((long long)H * runs, NT, 4096)), dim3(NT), 0, stream,
-                       labels, Sink{H, W, area, border, nullptr, nullptr, 0}, runs, vec);
+    launch_accumulate(AreaPlanes{H, W, labels, area, border}, stream);
     return fg::launched("regions_stats");
 }
 
@@ -387,12 +317,9 @@ FG_API int fg_regions_table(const int* labels, const int* rank, int H, int W, lo
         return fg::fail(FG_ERR_INVALID, "%s: %d regions in a scene of %d x %d", who, R, H, W);
     if (!aligned(labels, 4) || !aligned(rank, 4) || !aligned(table, 8))
         return fg::fail(FG_ERR_INVALID, "%s: labels and ranks must be 4-byte, the table 8-byte aligned", who);
-    const Sink k{H, W, nullptr, nullptr, rank, table, R};
-    const int runs = (W + RUN - 1) / RUN;
-    const int vec = W % RUN == 0 && aligned(labels, 16);
-    hipLaunchKernelGGL(table_init_kernel, dim3(fg::blocks_for((long long)H * W, NT, 4096)), dim3(NT), 0, stream, labels, k);
-    hipLaunchKernelGGL(stats_kernel<true>, dim3(fg::blocks_for((long long)H * runs, NT, 4096)), dim3(NT), 0, stream,
-                       labels, k, runs, vec);
+    const BoxTable k{H, W, labels, rank, table, R};
+    hipLaunchKernelGGL(table_init_kernel, dim3(fg::blocks_for((long long)H * W, NT, 4096)), dim3(NT), 0, stream, k);
+    launch_accumulate(k, stream);
     return fg::launched("regions_table");
 }
 

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .regions import check_source
+from .regions import check_source, rank_plane, table_columns
 
 Q = 1024.0                       # quanta per unit of depth
 DEPTH_TABLE_COLUMNS = ("wet_area", "depth_sum_q", "depth_max_q")
@@ -79,34 +79,28 @@ def flood_depth(mask, elevation, regions=None, pixel_area=1.0):
                          f"{elevation.device})")
     if H < 1 or W < 1 or H > ops.MAX_SEED_SIDE or W > ops.MAX_SEED_SIDE:
         raise ValueError(f"flood_depth: a scene of {H} x {W}: each side must be 1 .. {ops.MAX_SEED_SIDE}")
-    R = 0
     if regions is not None:
         if regions.get("table") is None:
             raise ValueError("flood_depth: the regions were computed with table=False")
         if tuple(regions["labels"].shape) != (H, W) or regions["labels"].device != mask.device:
             raise ValueError(f"flood_depth: the regions' labels are {tuple(regions['labels'].shape)} on "
                              f"{regions['labels'].device} for a mask of {H} x {W} on {mask.device}")
-        R = len(regions["table"]["label"])
     dev = mask.device
     mask, elevation = mask.contiguous(), elevation.contiguous()
     shore = ops.shore(mask, torch.empty((1, 1, H, W), dtype=torch.float32, device=dev))
     near, _ = ops.nearest_seed(shore, "threshold", True, torch.empty((H, W), dtype=torch.int32, device=dev))
     depth = ops.flood_depth(mask, elevation, near, torch.empty((1, 1, H, W), dtype=torch.float32, device=dev))
     scene = ops.depth_table(None, None, depth, torch.empty((1, 3), dtype=torch.int64, device=dev))
-    tab = None
-    if R:
-        rank = torch.empty((H, W), dtype=torch.int32, device=dev)
-        roots = torch.from_numpy(np.ascontiguousarray(regions["table"]["label"])).to(dev)
-        rank.view(-1)[roots] = torch.arange(R, dtype=torch.int32, device=dev)
-        tab = ops.depth_table(regions["labels"], rank, depth, torch.empty((R, 3), dtype=torch.int64, device=dev))
+    R, rank = rank_plane(regions["labels"], regions["table"]["label"]) if regions is not None else (0, None)
+    tab = ops.depth_table(regions["labels"], rank, depth,
+                          torch.empty((R, 3), dtype=torch.int64, device=dev)) if R else None
     flooded = int(ops.flood_count(mask.view(1, 1, H, W)).cpu())
     row = scene.cpu().numpy()[0]
     res = {"depth": depth, "nearest_shore": near, "shore_count": int(ops.flood_count(shore).cpu()),
            "wet_area": int(row[0])}
     res["max_depth"], res["mean_depth"], res["volume"] = _totals(row, flooded, pixel_area)
     if regions is not None:
-        cols = tab.cpu().numpy() if R else np.zeros((0, 3), dtype=np.int64)
-        table = {name: np.ascontiguousarray(cols[:, j]) for j, name in enumerate(DEPTH_TABLE_COLUMNS)}
+        table = table_columns(tab, DEPTH_TABLE_COLUMNS)
         total = table["depth_sum_q"].astype(np.float64) / Q
         table["mean_depth"] = total / regions["table"]["area"].astype(np.float64)
         table["max_depth"] = table["depth_max_q"].astype(np.float64) / Q

@@ -1179,11 +1179,17 @@ REGION_KINDS = {"threshold": L.FG_SCALAR_THRESHOLD, "logit": L.FG_SCALAR_LOGIT}
 REGION_MODES = {"remove": L.FG_REGIONS_REMOVE, "fill": L.FG_REGIONS_FILL}
 
 
-def _int_plane(t, H, W, what, dtype=torch.int32):
-    if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (H, W) and t.is_contiguous()):
-        raise RuntimeError(f"floodgan regions: {what} is a contiguous {dtype} [{H}, {W}] device tensor (got "
+def _plane(t, H, W, what, dtype=torch.int32):
+    """t holds one contiguous H x W plane of dtype on the device ([H, W], or with leading dimensions of 1)"""
+    if not (t.is_cuda and t.dtype == dtype and t.numel() == H * W and tuple(t.shape[-2:]) == (H, W)
+            and t.is_contiguous()):
+        raise RuntimeError(f"floodgan scene: {what} is a contiguous {dtype} [{H}, {W}] device tensor (got "
                            f"{t.dtype} {tuple(t.shape)} on {t.device})")
-    return t
+
+
+def _table(t, k):
+    if not (t.is_cuda and t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == k and t.is_contiguous()):
+        raise RuntimeError(f"floodgan scene: the table is a contiguous int64 [R, {k}] device tensor")
 
 
 def region_source(t):
@@ -1201,7 +1207,7 @@ def regions_label(src, kind, target, connectivity, labels):
     `target` of channel 0 of src ([1, C, H, W], any strides), -1 on the other class"""
     _, _, H, W = src.shape
     L.require_device(src, "region source")
-    _int_plane(labels, H, W, "the labels plane")
+    _plane(labels, H, W, "the labels plane")
     L.check(_lib().fg_regions_label(sview(src), H, W, REGION_KINDS[kind], int(bool(target)), int(connectivity),
                                     L.ptr(labels), L.stream_handle()), "regions_label")
     return labels
@@ -1211,7 +1217,7 @@ def regions_stats(labels, area, border):
     """fg_regions_stats: area / border (int32 [H, W]) at every root's index, 0 elsewhere"""
     H, W = labels.shape
     for t, what in ((labels, "the labels plane"), (area, "the area plane"), (border, "the border plane")):
-        _int_plane(t, H, W, what)
+        _plane(t, H, W, what)
     L.check(_lib().fg_regions_stats(L.ptr(labels), H, W, L.ptr(area), L.ptr(border), L.stream_handle()),
             "regions_stats")
 
@@ -1219,11 +1225,9 @@ def regions_stats(labels, area, border):
 def regions_table(labels, rank, table):
     """fg_regions_table: table (int64 [R, 8]) from the labels and the rank plane"""
     H, W = labels.shape
-    _int_plane(labels, H, W, "the labels plane")
-    _int_plane(rank, H, W, "the rank plane")
-    if not (table.is_cuda and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 8
-            and table.is_contiguous()):
-        raise RuntimeError("floodgan regions: the table is a contiguous int64 [R, 8] device tensor")
+    _plane(labels, H, W, "the labels plane")
+    _plane(rank, H, W, "the rank plane")
+    _table(table, 8)
     L.check(_lib().fg_regions_table(L.ptr(labels), L.ptr(rank), H, W, L.ptr(table), table.shape[0],
                                     L.stream_handle()), "regions_table")
 
@@ -1232,13 +1236,11 @@ def regions_apply(labels, area, border, mode, min_area, mask, counts):
     """fg_regions_apply: one sieve step ("remove" / "fill") into mask (fp32 [H, W] or [1, 1, H, W], contiguous);
     counts (int64 [2]) = components and pixels changed"""
     H, W = labels.shape
-    _int_plane(labels, H, W, "the labels plane")
+    _plane(labels, H, W, "the labels plane")
     for t, what in ((area, "the area plane"), (border, "the border plane")):
         if t is not None:
-            _int_plane(t, H, W, what)
-    L.require_device(mask, "region mask")
-    if mask.numel() != H * W or tuple(mask.shape[-2:]) != (H, W) or not mask.is_contiguous():
-        raise RuntimeError(f"floodgan regions: the mask is a contiguous fp32 [{H}, {W}] tensor (got {tuple(mask.shape)})")
+            _plane(t, H, W, what)
+    _plane(mask, H, W, "the mask", torch.float32)
     if not (counts.is_cuda and counts.dtype == torch.int64 and tuple(counts.shape) == (2,) and counts.is_contiguous()):
         raise RuntimeError("floodgan regions: counts is an int64 [2] device tensor")
     wrote(mask)
@@ -1251,23 +1253,15 @@ def regions_apply(labels, area, border, mode, min_area, mask, counts):
 MAX_SEED_SIDE = 32768           # fg_nearest_seed: 2 * 32767^2 still fits the int32 squared distance
 
 
-def _float_plane(t, H, W, what):
-    L.require_device(t, what)
-    if t.numel() != H * W or tuple(t.shape[-2:]) != (H, W) or not t.is_contiguous():
-        raise RuntimeError(f"floodgan depth: {what} is a contiguous fp32 [{H}, {W}] device tensor (got "
-                           f"{tuple(t.shape)})")
-    return t
-
-
 def nearest_seed(src, kind, target, nearest, dist2=None):
     """fg_nearest_seed: nearest (int32 [H, W]) = the index of the nearest pixel of class `target` of channel 0 of src
     ([1, C, H, W], any strides), ties to the smallest index, dist2 (int32 [H, W] or None) its squared distance; -1
     in both without a seed.  The scratch (column plane and seed bits) is allocated here, per call."""
     _, _, H, W = src.shape
     L.require_device(src, "seed source")
-    _int_plane(nearest, H, W, "the nearest plane")
+    _plane(nearest, H, W, "the nearest plane")
     if dist2 is not None:
-        _int_plane(dist2, H, W, "the squared-distance plane")
+        _plane(dist2, H, W, "the squared-distance plane")
     nbytes = int(_lib().fg_nearest_seed_scratch_bytes(H, W))
     if nbytes <= 0:
         raise RuntimeError(f"floodgan depth: a scene of {H} x {W}: each side must be 1 .. {MAX_SEED_SIDE}")
@@ -1281,8 +1275,8 @@ def shore(mask, out):
     """fg_shore: out (fp32 [H, W] or [1, 1, H, W]) = 1 on the flood pixels of the 0 / 1 mask with a dry 4-neighbour
     inside the scene, else 0"""
     H, W = int(mask.shape[-2]), int(mask.shape[-1])
-    _float_plane(mask, H, W, "the mask")
-    _float_plane(out, H, W, "the shore plane")
+    _plane(mask, H, W, "the mask", torch.float32)
+    _plane(out, H, W, "the shore plane", torch.float32)
     wrote(out)
     L.check(_lib().fg_shore(L.ptr(mask), H, W, L.ptr(out), L.stream_handle()), "shore")
     return out
@@ -1291,10 +1285,10 @@ def shore(mask, out):
 def flood_depth(mask, elevation, nearest, depth):
     """fg_flood_depth: depth = max(elevation[nearest] - elevation, 0) on the flood pixels of mask, 0 elsewhere"""
     H, W = nearest.shape
-    _float_plane(mask, H, W, "the mask")
-    _float_plane(elevation, H, W, "the elevation")
-    _int_plane(nearest, H, W, "the nearest plane")
-    _float_plane(depth, H, W, "the depth plane")
+    _plane(mask, H, W, "the mask", torch.float32)
+    _plane(elevation, H, W, "the elevation", torch.float32)
+    _plane(nearest, H, W, "the nearest plane")
+    _plane(depth, H, W, "the depth plane", torch.float32)
     wrote(depth)
     L.check(_lib().fg_flood_depth(L.ptr(mask), L.ptr(elevation), L.ptr(nearest), H, W, L.ptr(depth),
                                   L.stream_handle()), "flood_depth")
@@ -1305,15 +1299,13 @@ def depth_table(labels, rank, depth, table):
     """fg_depth_table: table (int64 [R, 3]) = {wet_area, depth_sum_q, depth_max_q} per region of the labels / rank
     planes; both None: the whole scene as one region (R = 1)"""
     H, W = int(depth.shape[-2]), int(depth.shape[-1])
-    _float_plane(depth, H, W, "the depth plane")
+    _plane(depth, H, W, "the depth plane", torch.float32)
     if (labels is None) != (rank is None):
         raise RuntimeError("floodgan depth: labels and rank plane come together")
     if labels is not None:
-        _int_plane(labels, H, W, "the labels plane")
-        _int_plane(rank, H, W, "the rank plane")
-    if not (table.is_cuda and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 3
-            and table.is_contiguous()):
-        raise RuntimeError("floodgan depth: the table is a contiguous int64 [R, 3] device tensor")
+        _plane(labels, H, W, "the labels plane")
+        _plane(rank, H, W, "the rank plane")
+    _table(table, 3)
     L.check(_lib().fg_depth_table(L.ptr(labels), L.ptr(rank), L.ptr(depth), H, W, L.ptr(table), table.shape[0],
                                   L.stream_handle()), "depth_table")
     return table

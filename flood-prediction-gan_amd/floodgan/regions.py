@@ -75,16 +75,34 @@ def label_regions(src, kind="logit", target=True, connectivity=8):
 def region_table(labels):
     """(R, table) of a labels plane: table an int64 [R, 8] device tensor in COLUMNS order, rows in ascending label
     order; one device -> host read (the number of roots).  R = 0 gives an empty table without a launch."""
-    H, W = labels.shape
-    flat = labels.view(-1)
-    roots = torch.nonzero(flat == torch.arange(H * W, dtype=torch.int32, device=labels.device)).view(-1)
-    R = int(roots.numel())
+    R, rank = rank_plane(labels)
     table = torch.empty((R, 8), dtype=torch.int64, device=labels.device)
     if R:
-        rank = torch.empty((H, W), dtype=torch.int32, device=labels.device)
-        rank.view(-1)[roots] = torch.arange(R, dtype=torch.int32, device=labels.device)
         ops.regions_table(labels, rank, table)
     return R, table
+
+
+def rank_plane(labels, roots=None):
+    """(R, rank): rank an int32 [H, W] device plane that holds 0 .. R - 1 at the R roots of a labels plane, in ascending
+    order (None when R = 0).  roots: their indices (int64 numpy) where the caller has them; else they are found here,
+    with one device -> host read (their number)."""
+    dev = labels.device
+    if roots is None:
+        roots = torch.nonzero(labels.view(-1) == torch.arange(labels.numel(), dtype=torch.int32, device=dev)).view(-1)
+    else:
+        roots = torch.from_numpy(np.ascontiguousarray(roots)).to(dev)
+    R = int(roots.numel())
+    if not R:
+        return 0, None
+    rank = torch.empty_like(labels)
+    rank.view(-1)[roots] = torch.arange(R, dtype=torch.int32, device=dev)
+    return R, rank
+
+
+def table_columns(table, names):
+    """{name: int64 numpy [R]} of an int64 [R, len(names)] device table (one device -> host read); None: no rows"""
+    cols = table.cpu().numpy() if table is not None else np.zeros((0, len(names)), dtype=np.int64)
+    return {name: np.ascontiguousarray(cols[:, j]) for j, name in enumerate(names)}
 
 
 def flood_regions(src, kind="logit", min_region=1, min_hole=0, connectivity=8, table=True):
@@ -123,8 +141,7 @@ def flood_regions(src, kind="logit", min_region=1, min_hole=0, connectivity=8, t
     res = {"mask": mask, "labels": labels, "table": None, "centroids": None}
     if table:
         R, tab = region_table(labels)
-        cols = tab.cpu().numpy()
-        res["table"] = {name: np.ascontiguousarray(cols[:, j]) for j, name in enumerate(COLUMNS)}
+        res["table"] = table_columns(tab, COLUMNS)
         a = res["table"]["area"].astype(np.float64)
         res["centroids"] = np.stack([res["table"]["sum_y"] / a, res["table"]["sum_x"] / a], axis=1)
     else:

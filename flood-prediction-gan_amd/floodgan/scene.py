@@ -197,10 +197,10 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
     ys, xs = ([0], [0]) if whole else window_grid(H, W, tile, overlap)
     unet = None
     sieve = min_region is not None or min_hole is not None
+    min_region, min_hole = 1 if min_region is None else int(min_region), 0 if min_hole is None else int(min_hole)
     if sieve:
         if seg_model is None:
             raise ValueError("predict_scene: min_region / min_hole sieve the flood mask and need seg_model")
-        min_region, min_hole = 1 if min_region is None else int(min_region), 0 if min_hole is None else int(min_hole)
         if min_region < 0 or min_hole < 0 or connectivity not in (4, 8):
             raise ValueError(f"predict_scene: min_region {min_region} and min_hole {min_hole} must not be negative, "
                              f"connectivity {connectivity!r} must be 4 or 8")
@@ -236,19 +236,15 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
                 logits = ml.result()
             res["flood_logits"] = logits
             res["flood_fraction"] = int(ops.flood_count(logits).cpu()) / (H * W)
-            if sieve:
+            if sieve or elevation is not None:
                 from .regions import flood_regions
-                regions = flood_regions(logits, "logit", min_region, min_hole, connectivity)
+                regions = flood_regions(logits, "logit", min_region, min_hole, connectivity)     # (1, 0: no sieve)
                 res["flood_mask"] = regions.pop("mask")
                 res["regions"] = regions
-                res["flood_fraction_sieved"] = regions["flood_fraction"]
+                if sieve:
+                    res["flood_fraction_sieved"] = regions["flood_fraction"]
             if elevation is not None:
                 from .depth import flood_depth
-                if not sieve:
-                    from .regions import flood_regions
-                    regions = flood_regions(logits, "logit", 1, 0, connectivity)
-                    res["flood_mask"] = regions.pop("mask")
-                    res["regions"] = regions
                 depth = flood_depth(res["flood_mask"], elevation, res["regions"], pixel_area)
                 res["flood_depth"] = depth.pop("depth")
                 res["depth"] = depth

@@ -237,6 +237,71 @@ def test_flood_depth_equals_the_oracle(H, W, sieve, special):
         assert want["wet_area"] > 300 and want["table"]["wet_area"].min() > 0 and want["max_depth"] > 32
 
 
+# ---- the accumulation kernel behind the three tables (csrc/scene_common.hpp)
+
+@functools.lru_cache(maxsize=None)
+def _oracle_tables(H, W, name):
+    """(labels, region table, depth plane, depth table, the scene's depth row) of a pattern.  The depths hold zeros,
+    values that round to no quantum (2^-11 is a tie to even), negatives, ordinary values and values above the 2^20
+    cap."""
+    lab = RO.label_class(_seeds(H, W, name), True, 8)
+    values = np.array([0.0, 2.0 ** -12, 2.0 ** -11, 3 * 2.0 ** -11, -1.0, 0.5, 37.25, 2.0 ** 20, 2.0 ** 21],
+                      dtype=np.float32)
+    d = values[np.random.default_rng(H * W).integers(0, len(values), (H, W))]
+    q = DO.quanta(d)
+    scene = np.array([(q > 0).sum(), q[q > 0].sum(), q.max()], dtype=np.int64)
+    for a in (lab, d):
+        a.setflags(write=False)
+    return lab, RO.table(lab), d, DO.depth_table(lab, d), scene
+
+
+def _placed(values, shift):
+    """values [H, W] as a contiguous device view that starts `shift` elements into a fresh buffer"""
+    H, W = values.shape
+    host = torch.from_numpy(values.copy())
+    buf = torch.empty(H * W + 4, dtype=host.dtype, device=DEV)
+    view = buf[shift:shift + H * W].view(H, W)
+    view.copy_(host)
+    assert view.is_contiguous() and view.data_ptr() % 16 == values.itemsize * shift
+    return view
+
+
+@pytest.mark.parametrize("H,W", [(33, 64), (16, 16)])
+def test_the_three_tables_take_a_16_byte_and_a_4_byte_aligned_labels_plane(H, W):
+    """W is a multiple of the run of 4, so a 16-byte aligned labels plane is read by 16-byte loads and one that starts
+    4 bytes later pixel by pixel.  33 x 64 is 528 runs: two full blocks and a third of one partial wave and three
+    empty ones, which the whole-wave loop bound has to carry; 16 x 16 is a single wave."""
+    from floodgan import ops
+    from floodgan.regions import rank_plane
+    for name in ("bernoulli_0.593", "spiral", "flood", "frame_island"):
+        lab, want, d, want_depth, want_scene = _oracle_tables(H, W, name)
+        roots, R = want["label"], len(want["label"])
+        want_area, want_border = np.zeros(H * W, dtype=np.int32), np.zeros(H * W, dtype=np.int32)
+        want_area[roots] = want["area"]
+        want_border[roots] = (want["y0"] == 0) | (want["x0"] == 0) | (want["y1"] == H - 1) | (want["x1"] == W - 1)
+        depth = _placed(d, 0)
+        for shift in (0, 1):
+            what = (name, shift)
+            labels = _placed(lab, shift)
+            assert labels.data_ptr() % 16 == (0, 4)[shift]
+            area, border = (torch.full((H, W), 77, dtype=torch.int32, device=DEV) for _ in range(2))
+            ops.regions_stats(labels, area, border)
+            assert np.array_equal(area.cpu().numpy().ravel(), want_area), what
+            assert np.array_equal(border.cpu().numpy().ravel(), want_border), what
+            got_R, rank = rank_plane(labels)
+            assert got_R == R > 0, what
+            table = torch.full((R, 8), 77, dtype=torch.int64, device=DEV)
+            ops.regions_table(labels, rank, table)
+            for j, col in enumerate(RO.COLUMNS):
+                assert np.array_equal(table[:, j].cpu().numpy(), want[col]), (what, col)
+            got = ops.depth_table(labels, rank, depth, torch.full((R, 3), 77, dtype=torch.int64, device=DEV))
+            for j, col in enumerate(("wet_area", "depth_sum_q", "depth_max_q")):
+                assert np.array_equal(got[:, j].cpu().numpy(), want_depth[col]), (what, col)
+        got = ops.depth_table(None, None, depth, torch.full((1, 3), 77, dtype=torch.int64, device=DEV))
+        assert np.array_equal(got.cpu().numpy()[0], want_scene), name
+        assert want_scene[2] == 2 ** 30 and 0 < want_scene[0] < H * W                 # capped, and some pixels left out
+
+
 # ---- refused calls
 
 def test_refused_calls_leave_their_outputs_as_they_were():
