@@ -503,7 +503,7 @@ class Model:
 
     def predict_scene(self, input_path, tile=None, overlap=64, batch=8, seg_model_path=None, batch_stats=False,
                       out_dir=None, min_region=None, min_hole=None, connectivity=8, depth=False, pixel_area=1.0,
-                      depth_vmax=None):
+                      depth_vmax=None, polygons=False, transform=None):
         """Not in the reference: the predicted post-flood picture of a whole pre-flood scene, a TIFF of any size that
         need not be a dataset tile (floodgan.data.load_scene, floodgan.scene.predict_scene: overlapping windows
         through the generator -- pre_to_post for the cycle models -- blended on the device).  tile=None: the size the
@@ -520,8 +520,12 @@ class Model:
         rendering of clamp(depth / vmax, 0, 1), vmax = depth_vmax, or the scene's maximum depth, or 1 when that is
         0 --, {name}_floodMask.png and {name}_floodRegions.csv are written as with the minima (off unless given),
         the CSV with the depth columns, and the returned dict gains "flood_depth" (the picture's path), "max_depth",
-        "mean_depth" and "volume".  Out of scope: attention-mask mosaics, reflect-padding of scenes smaller
-        than a window, GeoTIFF output."""
+        "mean_depth" and "volume".  With polygons=True (it needs seg_model_path) the regions are traced into
+        polygons on the device (floodgan.outline) and written as {name}_floodRegions.geojson beside the CSV -- one
+        Polygon per region with the CSV's columns as properties, positions [x, y] in pixel corners or, with
+        `transform` (a GDAL-order 6-tuple), in its coordinates -- with the mask and the CSV as with the minima (off
+        unless given); the returned dict gains "polygons" (the file's path).  Out of scope: attention-mask mosaics,
+        reflect-padding of scenes smaller than a window, GeoTIFF output."""
         import os
 
         from .data import load_scene, load_scene_elevation
@@ -535,6 +539,9 @@ class Model:
         if tile is None:
             tile = self.resize if self.resize else 512
         elevation = None
+        if polygons and seg_model_path is None:
+            raise ValueError("predict_scene: polygons=True outlines the regions of the flood mask and needs "
+                             "seg_model_path")
         if depth:
             if seg_model_path is None:
                 raise ValueError("predict_scene: depth=True gives the depth of the flood mask and needs seg_model_path")
@@ -545,7 +552,8 @@ class Model:
         generator = self.pre_to_post_generator if self.model_is_cycle else self.generator
         res = predict_scene(generator, x, tile=tile, overlap=overlap, batch=batch, seg_model=seg_model_path,
                             batch_stats=batch_stats, min_region=min_region, min_hole=min_hole,
-                            connectivity=connectivity, elevation=elevation, pixel_area=pixel_area)
+                            connectivity=connectivity, elevation=elevation, pixel_area=pixel_area,
+                            polygons=bool(polygons))
         os.makedirs(out_dir, exist_ok=True)
         name = scene_name(input_path)
         written = {"prediction": save_image(f"{out_dir}/{name}_prediction.png", res["output"], "rgb"),
@@ -556,6 +564,10 @@ class Model:
             written["regions"] = write_regions_csv(f"{out_dir}/{name}_floodRegions.csv", res["regions"],
                                                    res.get("depth"))
             written["region_count"] = res["regions"]["count"]
+            if polygons:
+                from .outline import write_regions_geojson
+                written["polygons"] = write_regions_geojson(f"{out_dir}/{name}_floodRegions.geojson", res["regions"],
+                                                            res["outlines"], res.get("depth"), transform)
             if depth:
                 vmax = depth_vmax if depth_vmax is not None else (res["depth"]["max_depth"] or 1.0)
                 # (a tensor divisor: one correctly rounded fp32 division per pixel, not a product with 1 / vmax)

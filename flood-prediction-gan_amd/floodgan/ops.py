@@ -1309,3 +1309,71 @@ def depth_table(labels, rank, depth, table):
     L.check(_lib().fg_depth_table(L.ptr(labels), L.ptr(rank), L.ptr(depth), H, W, L.ptr(table), table.shape[0],
                                   L.stream_handle()), "depth_table")
     return table
+
+
+# ------------------------------------------------------------------------------------------ region outlines (outline.hip)
+
+MAX_OUTLINE_PIXELS = 2 ** 29    # fg_outline_*: the edge key 4 (y W + x) + side is an int32
+
+
+def _array(t, n, what, dtype=torch.int32):
+    if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (n,) and t.is_contiguous()):
+        raise RuntimeError(f"floodgan outline: {what} is a contiguous {dtype} [{n}] device tensor (got {t.dtype} "
+                           f"{tuple(t.shape)} on {t.device})")
+
+
+def outline_launches(E):
+    """fg_outline_launches: the launches of an outline of E cracks, 4 + 2 ceil(log2 E) (1 for E = 0)"""
+    return int(_lib().fg_outline_launches(int(E)))
+
+
+def outline_cracks(labels, sides, count):
+    """fg_outline_cracks: sides (uint8 [H, W]) = the 4-bit crack mask of every pixel of the labels plane, count (int32
+    [H, W]) = its number of cracks"""
+    H, W = labels.shape
+    _plane(labels, H, W, "the labels plane")
+    _plane(sides, H, W, "the side plane", torch.uint8)
+    _plane(count, H, W, "the count plane")
+    L.check(_lib().fg_outline_cracks(L.ptr(labels), H, W, L.ptr(sides), L.ptr(count), L.stream_handle()),
+            "outline_cracks")
+
+
+def outline_rings(labels, sides, incl, connectivity, out):
+    """fg_outline_rings: per crack its key, its ring's start and the suffix sums of its ring, into out = {key, ring,
+    edges, corners: int32 [E], signed2: int64 [E], corner: uint8 [E]}; incl: the inclusive int32 prefix sum of the
+    counts, [H * W].  The scratch (40 bytes per crack) is allocated here, per call."""
+    H, W = labels.shape
+    E = int(out["key"].shape[0])
+    _plane(labels, H, W, "the labels plane")
+    _plane(sides, H, W, "the side plane", torch.uint8)
+    _array(incl, H * W, "the prefix sum")
+    for name in ("key", "ring", "edges", "corners"):
+        _array(out[name], E, f"the {name} array")
+    _array(out["signed2"], E, "the signed2 array", torch.int64)
+    _array(out["corner"], E, "the corner array", torch.uint8)
+    nbytes = int(_lib().fg_outline_scratch_bytes(E))
+    if nbytes <= 0:
+        raise RuntimeError(f"floodgan outline: {E} cracks (at least one)")
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=labels.device)
+    L.check(_lib().fg_outline_rings(L.ptr(labels), L.ptr(sides), L.ptr(incl), H, W, int(connectivity), E,
+                                    L.ptr(out["key"]), L.ptr(out["ring"]), L.ptr(out["edges"]), L.ptr(out["corners"]),
+                                    L.ptr(out["signed2"]), L.ptr(out["corner"]), L.ptr(scratch), L.stream_handle()),
+            "outline_rings")
+    return out
+
+
+def outline_vertices(out, base, H, W, vertices):
+    """fg_outline_vertices: vertices (int32 [V, 2], (y, x)) from outline_rings' arrays and base (int32 [E]: at every
+    ring's start the row where its corners begin)"""
+    E = int(out["key"].shape[0])
+    for name in ("key", "ring", "corners"):
+        _array(out[name], E, f"the {name} array")
+    _array(out["corner"], E, "the corner array", torch.uint8)
+    _array(base, E, "the base array")
+    if not (vertices.is_cuda and vertices.dtype == torch.int32 and vertices.dim() == 2 and vertices.shape[1] == 2
+            and vertices.is_contiguous()):
+        raise RuntimeError("floodgan outline: the vertices are a contiguous int32 [V, 2] device tensor")
+    L.check(_lib().fg_outline_vertices(L.ptr(out["key"]), L.ptr(out["ring"]), L.ptr(out["corners"]),
+                                       L.ptr(out["corner"]), L.ptr(base), int(H), int(W), E, vertices.shape[0],
+                                       L.ptr(vertices), L.stream_handle()), "outline_vertices")
+    return vertices

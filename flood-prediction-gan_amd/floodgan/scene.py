@@ -10,7 +10,8 @@ device (csrc/mosaic.hip: fg_mosaic_accumulate, fg_mosaic_finalize).  Not in the 
   window_weight  the integer blending weight of a window-local coordinate
   Mosaic         the fp32 accumulation planes and the device grid: .windows / .add / .result
   predict_scene  scene -> generator output, and with a segmentation U-Net its flood logits and flood fraction; with
-                 min_region / min_hole also the sieved flood mask and its regions (floodgan.regions)
+                 min_region / min_hole also the sieved flood mask and its regions (floodgan.regions), with polygons
+                 their outlines (floodgan.outline)
 
 Grid.  Along an axis of length L, with S = tile - overlap, the starts are the sorted unique values of
 min(i S, L - tile), i = 0 .. ceil((L - tile) / S): every window lies inside the scene, the last one shifted inward
@@ -155,7 +156,7 @@ def _flood_logits(unet, images, batch_stats):
 
 
 def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, batch_stats=False, min_region=None,
-                  min_hole=None, connectivity=8, elevation=None, pixel_area=1.0):
+                  min_hole=None, connectivity=8, elevation=None, pixel_area=1.0, polygons=False):
     """A device scene x [1, C, H, W] in [-1, 1] through `generator` in windows of tile x tile pixels, `batch` at a
     time (the last batch may be smaller), blended by Mosaic.  Runs under torch.no_grad() with torch.manual_seed(47)
     before each generator call, as the package's picture paths do; the generator runs in the mode it is in.
@@ -176,9 +177,16 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
     regions and `pixel_area`) -- of the sieved mask when minima are given, else of the plain decision, which the
     result then also carries as "flood_mask" and "regions" (flood_regions with the minima off).  The result gains
     "flood_depth" (fp32 [1, 1, H, W]) and "depth" (flood_depth's dict without its plane).
+    polygons=True (with seg_model; ValueError without, before any launch): the outlines of the regions
+    (floodgan.outline.region_outlines of the regions' labels at `connectivity`), with "flood_mask" and "regions" as
+    `elevation` gives them (the minima off unless given).  The result gains "outlines".
     Out of scope: attention-mask mosaics, reflect-padding of scenes smaller than a window, GeoTIFF output."""
     if elevation is not None and seg_model is None:
         raise ValueError("predict_scene: elevation gives the depth of the flood mask and needs seg_model")
+    if polygons and seg_model is None:
+        raise ValueError("predict_scene: polygons=True outlines the regions of the flood mask and needs seg_model")
+    if polygons and connectivity not in (4, 8):
+        raise ValueError(f"predict_scene: connectivity {connectivity!r} must be 4 or 8")
     require_device(x, "scene")
     if x.dim() != 4 or x.shape[0] != 1:
         raise ValueError(f"predict_scene: a [1, C, H, W] scene (got {tuple(x.shape)})")
@@ -236,7 +244,7 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
                 logits = ml.result()
             res["flood_logits"] = logits
             res["flood_fraction"] = int(ops.flood_count(logits).cpu()) / (H * W)
-            if sieve or elevation is not None:
+            if sieve or elevation is not None or polygons:
                 from .regions import flood_regions
                 regions = flood_regions(logits, "logit", min_region, min_hole, connectivity)     # (1, 0: no sieve)
                 res["flood_mask"] = regions.pop("mask")
@@ -248,6 +256,9 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
                 depth = flood_depth(res["flood_mask"], elevation, res["regions"], pixel_area)
                 res["flood_depth"] = depth.pop("depth")
                 res["depth"] = depth
+            if polygons:
+                from .outline import region_outlines
+                res["outlines"] = region_outlines(res["regions"]["labels"], connectivity)
     return res
 
 

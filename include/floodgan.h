@@ -815,6 +815,54 @@ int fg_depth_table(const int* labels, const int* rank, const float* depth, int H
                    hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------- */
+/* region outlines: cracks, rings by pointer doubling, corner lists (not in the reference) */
+/* ---------------------------------------------------------------------------------------- */
+/* All of it is integer-exact and free of atomics.  A pixel (y, x) of an H x W labels plane (contiguous int32, as
+ * fg_regions_label writes it) is flood when its label is >= 0; everything outside the scene is dry.  A CRACK is a
+ * side of a flood pixel whose neighbour across it is dry, directed with the flood pixel on its left: side 0 top
+ * (y, x + 1) -> (y, x), 1 left (y, x) -> (y + 1, x), 2 bottom (y + 1, x) -> (y + 1, x + 1), 3 right (y + 1, x + 1)
+ * -> (y, x + 1).  Its KEY is 4 (y W + x) + side, an int32, so every entry refuses H * W >= 2^29; its COMPACT INDEX
+ * is its rank among the cracks in ascending key order.  The SUCCESSOR of a crack is the crack that starts at its end
+ * vertex; where two do (a saddle: two flood pixels touch diagonally) it is the right turn with connectivity 8 and the
+ * left turn with 4.  The cracks fall into cycles, the RINGS; a ring's START is its crack of the smallest key.  Every
+ * entry fails with FG_ERR_INVALID and writes nothing on a null pointer, a size or count that is not positive or too
+ * large, a misaligned pointer or a connectivity other than 4 or 8.  Indices the kernels read from device memory
+ * (offsets, side masks, successors, rings, bases) are checked against the array they index before use.
+ *
+ * fg_outline_cracks: sides[i] (uint8 [H, W]) = the 4-bit mask of pixel i's cracks (bit s: side s), count[i] (int32
+ * [H, W]) = their number.  One launch.  The caller scans the counts -- incl, their inclusive prefix sum as int32 --
+ * and reads E = incl[H W - 1] once.
+ *
+ * fg_outline_rings, for E >= 1 cracks: per compact index e (all arrays of length E, the caller's)
+ *   key[e]      the crack's key
+ *   ring[e]     the compact index of the start of e's ring
+ *   edges[e], corners[e], signed2[e]   the sums from e to the end of its ring, the ring cut in front of its start, of
+ *               1, of corner[.], and of x_i y_(i+1) - x_(i+1) y_i (int64) over a crack's vertices (y_i, x_i) ->
+ *               (y_(i+1), x_(i+1)): at a ring's start its number of cracks, its number of corners and twice its
+ *               signed area (negative for an outer ring, positive for a hole)
+ *   corner[e]   (uint8) 1 when the crack arriving at e's start vertex has another direction than e.
+ * 2 + 2 K launches, K = ceil(log2 E): the cracks' keys and successors; K rounds of pointer doubling for the ring
+ * minimum (m' = min(m, m[j]), j' = j[j]); the cut; K rounds of weighted list ranking.  Every round reads one buffer
+ * set and writes the other.  scratch: fg_outline_scratch_bytes(E) bytes (40 per crack, rounded up), 8-byte aligned,
+ * the caller's -- the library allocates nothing; with the outputs (25 per crack) that is 65 bytes per crack, and E is
+ * at most about 2 H W (a checkerboard).  fg_outline_scratch_bytes returns 0 for E <= 0; fg_outline_launches(E) is the
+ * number of launches of the three entries together, 4 + 2 K (1 for E <= 0: the cracks alone).
+ *
+ * fg_outline_vertices: base (int32 [E]) holds at every ring's start the row of `vertices` (contiguous int32 [V, 2],
+ * (y, x) per row) where the ring's corners begin (anything elsewhere).  A crack with corner[e] = 1 writes its start
+ * vertex at row base[ring[e]] + corners[ring[e]] - corners[e]: the ring's corners in ring order, beginning with the
+ * first met from the start's start vertex on, that vertex included.  Rows no crack names are left as they were; a row
+ * outside 0 .. V - 1 is skipped.  One launch. */
+long long fg_outline_scratch_bytes(int E);
+int fg_outline_launches(int E);
+int fg_outline_cracks(const int* labels, int H, int W, unsigned char* sides, int* count, hipStream_t stream);
+int fg_outline_rings(const int* labels, const unsigned char* sides, const int* incl, int H, int W, int connectivity,
+                     int E, int* key, int* ring, int* edges, int* corners, long long* signed2, unsigned char* corner,
+                     void* scratch, hipStream_t stream);
+int fg_outline_vertices(const int* key, const int* ring, const int* corners, const unsigned char* corner,
+                        const int* base, int H, int W, int E, int V, int* vertices, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------- */
 /* tile data path                                                    */
 /* ---------------------------------------------------------------------------------------- */
 /* Host-side baseline TIFF decode, replacing tifffile.imread (models/data.py:64-68) for the files
