@@ -12,7 +12,8 @@ through a generator in overlapping windows blended on the device (floodgan.scene
 connected components, minimum-mapping-unit sieve, region table -- on the device (floodgan.regions); the flood depth
 of a scene from its mask and elevation -- exact nearest-shore transform, depth plane, per-region depth table -- on the
 device (floodgan.depth); the outlines of the regions as polygons, traced on the device, and their GeoJSON file
-(floodgan.outline).
+(floodgan.outline); the drainage of a scene's elevation -- D8 flow directions, flow accumulation, basins and path
+lengths -- on the device (floodgan.flow).
 """
 from ._lib import load as load_library  # noqa: F401
 from .model_architectures import (AttentionGANBlock, AttentionGANDiscriminator,  # noqa: F401
@@ -27,6 +28,7 @@ from .scene import Mosaic, predict_scene, window_grid  # noqa: F401
 from .regions import flood_regions, label_regions, write_regions_csv  # noqa: F401
 from .depth import flood_depth, nearest_seed  # noqa: F401
 from .outline import region_outlines, write_regions_geojson  # noqa: F401
+from .flow import flow_accumulation, flow_directions, render_flow  # noqa: F401
 from .data import load_scene_elevation  # noqa: F401
 
 __all__ = ["PairedAttentionGenerator", "PairedAttentionBlock", "PairedAttentionDiscriminator",
@@ -36,4 +38,4 @@ __all__ = ["PairedAttentionGenerator", "PairedAttentionBlock", "PairedAttentionD
            "load_lpips_weights", "Canvas", "colormap_lut", "save_image", "save_sheet", "sheet_layout", "write_png",
            "read_png", "compare_output_images", "Mosaic", "predict_scene", "window_grid", "flood_regions",
            "label_regions", "write_regions_csv", "nearest_seed", "flood_depth", "load_scene_elevation",
-           "region_outlines", "write_regions_geojson"]
+           "region_outlines", "write_regions_geojson", "flow_directions", "flow_accumulation", "render_flow"]

@@ -255,6 +255,13 @@ SIGNATURES = {
                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fg_outline_vertices": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                             C.c_int, C.c_void_p, C.c_void_p],
+    "fg_flow_rounds": [C.c_int, C.c_int],
+    "fg_flow_scratch_bytes": [C.c_int, C.c_int],
+    "fg_flow_directions": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "fg_flow_flats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "fg_flow_accumulate": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fg_flow_region_table": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                             C.c_void_p],
     "fg_tiff_probe": [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "fg_tiff_read": [C.c_char_p, C.c_void_p, C.c_longlong],
     "fg_tile_transform": [C.POINTER(fg_tile_batch), C.c_void_p],
@@ -266,7 +273,7 @@ RESTYPES = {"fg_bernoulli_mt_workspace_words": C.c_longlong, "fg_last_error": C.
             "fg_channel_sum_workspace_doubles": C.c_longlong, "fg_bce_logits_workspace_doubles": C.c_longlong,
             "fg_in_partials_workspace_doubles": C.c_longlong, "fg_conv1x1_wgrad_workspace_floats": C.c_longlong,
             "fg_lpips_workspace_doubles": C.c_longlong, "fg_nearest_seed_scratch_bytes": C.c_longlong,
-            "fg_outline_scratch_bytes": C.c_longlong}
+            "fg_outline_scratch_bytes": C.c_longlong, "fg_flow_scratch_bytes": C.c_longlong}
 
 _lib = None
 

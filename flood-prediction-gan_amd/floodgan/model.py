@@ -503,7 +503,7 @@ class Model:
 
     def predict_scene(self, input_path, tile=None, overlap=64, batch=8, seg_model_path=None, batch_stats=False,
                       out_dir=None, min_region=None, min_hole=None, connectivity=8, depth=False, pixel_area=1.0,
-                      depth_vmax=None, polygons=False, transform=None):
+                      depth_vmax=None, polygons=False, transform=None, drainage=False, flat_rounds=0):
         """Not in the reference: the predicted post-flood picture of a whole pre-flood scene, a TIFF of any size that
         need not be a dataset tile (floodgan.data.load_scene, floodgan.scene.predict_scene: overlapping windows
         through the generator -- pre_to_post for the cycle models -- blended on the device).  tile=None: the size the
@@ -524,7 +524,12 @@ class Model:
         polygons on the device (floodgan.outline) and written as {name}_floodRegions.geojson beside the CSV -- one
         Polygon per region with the CSV's columns as properties, positions [x, y] in pixel corners or, with
         `transform` (a GDAL-order 6-tuple), in its coordinates -- with the mask and the CSV as with the minima (off
-        unless given); the returned dict gains "polygons" (the file's path).  Out of scope: attention-mask mosaics,
+        unless given); the returned dict gains "polygons" (the file's path).  With drainage=True (a 9-channel file;
+        seg_model_path is not needed) the drainage of the elevation (floodgan.flow.flow_accumulation with
+        `flat_rounds`) is written as {name}_flowAccumulation.png -- the "attention" rendering of
+        floodgan.flow.render_flow --, the CSV and the GeoJSON, where they are written, gain max_accumulation and
+        pit_pixels, and the returned dict gains "flow_accumulation" (the picture's path) and "pit_count".  Out of
+        scope: attention-mask mosaics,
         reflect-padding of scenes smaller than a window, GeoTIFF output."""
         import os
 
@@ -548,12 +553,19 @@ class Model:
             if depth_vmax is not None and not depth_vmax > 0:
                 raise ValueError(f"predict_scene: depth_vmax {depth_vmax!r} must be positive")
             elevation = load_scene_elevation(input_path, self.device)
+        if drainage:
+            from .flow import check_flat_rounds
+            flat_rounds = check_flat_rounds(flat_rounds)
+            dem = elevation if elevation is not None else load_scene_elevation(input_path, self.device)
         x = load_scene(input_path, self.topography, self.device)
         generator = self.pre_to_post_generator if self.model_is_cycle else self.generator
         res = predict_scene(generator, x, tile=tile, overlap=overlap, batch=batch, seg_model=seg_model_path,
                             batch_stats=batch_stats, min_region=min_region, min_hole=min_hole,
                             connectivity=connectivity, elevation=elevation, pixel_area=pixel_area,
                             polygons=bool(polygons))
+        if drainage:                # (here and not through predict_scene: its elevation would also ask for the depth)
+            from .scene import add_drainage
+            add_drainage(res, dem, flat_rounds)
         os.makedirs(out_dir, exist_ok=True)
         name = scene_name(input_path)
         written = {"prediction": save_image(f"{out_dir}/{name}_prediction.png", res["output"], "rgb"),
@@ -562,12 +574,13 @@ class Model:
             from .regions import write_regions_csv
             written["flood_mask"] = save_image(f"{out_dir}/{name}_floodMask.png", res["flood_mask"], "mask_true")
             written["regions"] = write_regions_csv(f"{out_dir}/{name}_floodRegions.csv", res["regions"],
-                                                   res.get("depth"))
+                                                   res.get("depth"), res.get("flow"))
             written["region_count"] = res["regions"]["count"]
             if polygons:
                 from .outline import write_regions_geojson
                 written["polygons"] = write_regions_geojson(f"{out_dir}/{name}_floodRegions.geojson", res["regions"],
-                                                            res["outlines"], res.get("depth"), transform)
+                                                            res["outlines"], res.get("depth"), transform,
+                                                            res.get("flow"))
             if depth:
                 vmax = depth_vmax if depth_vmax is not None else (res["depth"]["max_depth"] or 1.0)
                 # (a tensor divisor: one correctly rounded fp32 division per pixel, not a product with 1 / vmax)
@@ -578,6 +591,11 @@ class Model:
                     written[key] = res["depth"][key]
         elif "flood_logits" in res:
             written["flood_mask"] = save_image(f"{out_dir}/{name}_floodMask.png", res["flood_logits"], "mask_logits")
+        if drainage:
+            from .flow import render_flow
+            unit = render_flow(res["flow"]["accumulation"])[None, None]
+            written["flow_accumulation"] = save_image(f"{out_dir}/{name}_flowAccumulation.png", unit, "attention")
+            written["pit_count"] = res["flow"]["pit_count"]
         if self.verbose:
             print(f"Saving the prediction of scene '{name}' to {written['prediction']}")
         self.last_scene = res

@@ -1377,3 +1377,71 @@ def outline_vertices(out, base, H, W, vertices):
                                        L.ptr(out["corner"]), L.ptr(base), int(H), int(W), E, vertices.shape[0],
                                        L.ptr(vertices), L.stream_handle()), "outline_vertices")
     return vertices
+
+
+# ------------------------------------------------------------------------------------------ flow routing (flow.hip)
+
+MAX_FLAT_ROUNDS = 32768         # fg_flow_flats
+
+
+def flow_rounds(H, W):
+    """fg_flow_rounds: the doubling rounds of an H x W scene, ceil(log2 max(H W, 2))"""
+    return int(_lib().fg_flow_rounds(int(H), int(W)))
+
+
+def flow_directions(elevation, directions):
+    """fg_flow_directions: directions (uint8 [H, W]) = the D8 code of every pixel of the elevation (fp32 [H, W] or
+    [1, 1, H, W], contiguous): 0 .. 7 the steepest-descent neighbour, 8 a pit, 255 nodata"""
+    H, W = int(elevation.shape[-2]), int(elevation.shape[-1])
+    _plane(elevation, H, W, "the elevation", torch.float32)
+    _plane(directions, H, W, "the direction plane", torch.uint8)
+    L.check(_lib().fg_flow_directions(L.ptr(elevation), H, W, L.ptr(directions), L.stream_handle()), "flow_directions")
+    return directions
+
+
+def flow_flats(elevation, directions, rounds, out, counts):
+    """fg_flow_flats: `rounds` rounds of the flat wave from `directions` (uint8 [H, W], left as it was) into out (uint8
+    [H, W]); counts (int32 [rounds]) = the pixels directed per round.  The second buffer of the ping-pong is allocated
+    here, per call."""
+    H, W = int(elevation.shape[-2]), int(elevation.shape[-1])
+    rounds = int(rounds)
+    _plane(elevation, H, W, "the elevation", torch.float32)
+    _plane(directions, H, W, "the direction plane", torch.uint8)
+    _plane(out, H, W, "the resolved direction plane", torch.uint8)
+    if not (counts.is_cuda and counts.dtype == torch.int32 and tuple(counts.shape) == (max(rounds, 0),)
+            and counts.is_contiguous()):
+        raise RuntimeError(f"floodgan flow: counts is a contiguous int32 [{rounds}] device tensor")
+    work = directions.clone()
+    L.check(_lib().fg_flow_flats(L.ptr(elevation), H, W, L.ptr(work), L.ptr(out), rounds,
+                                 L.ptr(counts) if rounds > 0 else L.ptr(None), L.stream_handle()), "flow_flats")
+    return out, counts
+
+
+def flow_accumulate(directions, acc, basin, length):
+    """fg_flow_accumulate: acc, basin, length (int32 [H, W]) from a direction plane (uint8 [H, W]).  The scratch (20
+    bytes per pixel) is allocated here, per call."""
+    H, W = int(directions.shape[-2]), int(directions.shape[-1])
+    _plane(directions, H, W, "the direction plane", torch.uint8)
+    for t, what in ((acc, "the accumulation plane"), (basin, "the basin plane"), (length, "the length plane")):
+        _plane(t, H, W, what)
+    nbytes = int(_lib().fg_flow_scratch_bytes(H, W))
+    if nbytes <= 0:
+        raise RuntimeError(f"floodgan flow: a scene of {H} x {W}: H * W must be positive and below 2^31")
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=directions.device)
+    L.check(_lib().fg_flow_accumulate(L.ptr(directions), H, W, L.ptr(acc), L.ptr(basin), L.ptr(length),
+                                      L.ptr(scratch), L.stream_handle()), "flow_accumulate")
+    return acc, basin, length
+
+
+def flow_region_table(labels, rank, acc, directions, table):
+    """fg_flow_region_table: table (int64 [R, 2]) = {max_accumulation, pit_pixels} per region of the labels / rank
+    planes"""
+    H, W = labels.shape
+    _plane(labels, H, W, "the labels plane")
+    _plane(rank, H, W, "the rank plane")
+    _plane(acc, H, W, "the accumulation plane")
+    _plane(directions, H, W, "the direction plane", torch.uint8)
+    _table(table, 2)
+    L.check(_lib().fg_flow_region_table(L.ptr(labels), L.ptr(rank), L.ptr(acc), L.ptr(directions), H, W, L.ptr(table),
+                                        table.shape[0], L.stream_handle()), "flow_region_table")
+    return table

@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .regions import DEPTH_COLUMNS
+from .regions import DEPTH_COLUMNS, FLOW_COLUMNS, flow_table
 
 MAX_PIXELS = ops.MAX_OUTLINE_PIXELS
 FEATURE_COLUMNS = ("label", "area", "y0", "x0", "y1", "x1")
@@ -130,13 +130,14 @@ def _position(y, x, transform):
     return [a + x * b + y * c, d + x * e + y * f]
 
 
-def write_regions_geojson(path, regions, outlines, depth=None, transform=None):
+def write_regions_geojson(path, regions, outlines, depth=None, transform=None, flow=None):
     """A GeoJSON FeatureCollection of a flood_regions result and the region_outlines of its labels: one Feature per
     region, in table order; the geometry a Polygon of the region's outer ring, then its holes, each closed by repeating
     its first position.  transform=None: positions are [x, y] as integers; a GDAL-order 6-tuple (a, b, c, d, e, f):
     [a + x b + y c, d + x e + y f] in fp64, written by repr.  Properties: label, area, y0, x0, y1, x1, centroid_y,
     centroid_x, perimeter (the sum of the region's ring `edges`), holes, and with `depth` (flood_depth with these
-    regions) wet_area, mean_depth, max_depth, volume.  Keys are written in a fixed order by the standard json module:
+    regions) wet_area, mean_depth, max_depth, volume, and with `flow` (flow_accumulation with the "table" of these
+    regions) max_accumulation, pit_pixels.  Keys are written in a fixed order by the standard json module:
     two writes give the same bytes.  Raises ValueError for regions computed with table=False, for a depth result
     without a table of these regions, and for outlines whose outer rings are not the table's regions.  Returns
     path."""
@@ -150,6 +151,7 @@ def write_regions_geojson(path, regions, outlines, depth=None, transform=None):
         if dtab is None or len(dtab["wet_area"]) != R:
             raise ValueError("write_regions_geojson: the depth result holds no table of these regions (flood_depth "
                              "with regions=)")
+    ftab = flow_table(flow, R, "write_regions_geojson")
     if transform is not None:
         transform = tuple(float(v) for v in transform)
         if len(transform) != 6:
@@ -178,6 +180,9 @@ def write_regions_geojson(path, regions, outlines, depth=None, transform=None):
             props["wet_area"] = int(dtab["wet_area"][r])
             for c in DEPTH_COLUMNS[1:]:
                 props[c] = float(dtab[c][r])
+        if ftab is not None:
+            for c in FLOW_COLUMNS:
+                props[c] = int(ftab[c][r])
         features.append({"type": "Feature", "properties": props,
                          "geometry": {"type": "Polygon", "coordinates": coords}})
     with open(path, "w") as f:

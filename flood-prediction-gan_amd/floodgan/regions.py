@@ -156,26 +156,45 @@ def flood_regions(src, kind="logit", min_region=1, min_hole=0, connectivity=8, t
 DEPTH_COLUMNS = ("wet_area", "mean_depth", "max_depth", "volume")
 
 
-def write_regions_csv(path, regions, depth=None):
+FLOW_COLUMNS = ("max_accumulation", "pit_pixels")
+
+
+def flow_table(flow, R, who):
+    """the {max_accumulation, pit_pixels} table of a flow result for R regions, or None without a flow result"""
+    if flow is None:
+        return None
+    ftab = flow.get("table")
+    if ftab is None or len(ftab["max_accumulation"]) != R:
+        raise ValueError(f"{who}: the flow result holds no table of these regions (floodgan.flow.flow_region_table)")
+    return ftab
+
+
+def write_regions_csv(path, regions, depth=None, flow=None):
     """One header line (COLUMNS, then centroid_y, centroid_x) and one line per region of a flood_regions result;
     integers as integers, the centroids by repr (they read back to the same fp64).  With `depth` (a
     floodgan.depth.flood_depth result computed with these regions) the lines gain DEPTH_COLUMNS: wet_area as an
-    integer, the others by repr.  Returns path."""
+    integer, the others by repr.  With `flow` (a floodgan.flow.flow_accumulation result that carries the "table" of
+    these regions) they gain FLOW_COLUMNS after those, as integers.  Returns path."""
     tab, cen = regions["table"], regions["centroids"]
     if tab is None:
         raise ValueError("write_regions_csv: the regions were computed with table=False")
     head, dtab = COLUMNS + ("centroid_y", "centroid_x"), None
+    ftab = flow_table(flow, len(tab["label"]), "write_regions_csv")
     if depth is not None:
         dtab = depth.get("table")
         if dtab is None or len(dtab["wet_area"]) != len(tab["label"]):
             raise ValueError("write_regions_csv: the depth result holds no table of these regions (flood_depth with "
                              "regions=)")
         head = head + DEPTH_COLUMNS
+    if ftab is not None:
+        head = head + FLOW_COLUMNS
     with open(path, "w") as f:
         f.write(",".join(head) + "\n")
         for r in range(len(tab["label"])):
             cells = [str(int(tab[c][r])) for c in COLUMNS] + [repr(float(cen[r, 0])), repr(float(cen[r, 1]))]
             if dtab is not None:
                 cells += [str(int(dtab["wet_area"][r]))] + [repr(float(dtab[c][r])) for c in DEPTH_COLUMNS[1:]]
+            if ftab is not None:
+                cells += [str(int(ftab[c][r])) for c in FLOW_COLUMNS]
             f.write(",".join(cells) + "\n")
     return path

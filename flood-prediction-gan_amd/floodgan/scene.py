@@ -156,7 +156,8 @@ def _flood_logits(unet, images, batch_stats):
 
 
 def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, batch_stats=False, min_region=None,
-                  min_hole=None, connectivity=8, elevation=None, pixel_area=1.0, polygons=False):
+                  min_hole=None, connectivity=8, elevation=None, pixel_area=1.0, polygons=False, drainage=False,
+                  flat_rounds=0):
     """A device scene x [1, C, H, W] in [-1, 1] through `generator` in windows of tile x tile pixels, `batch` at a
     time (the last batch may be smaller), blended by Mosaic.  Runs under torch.no_grad() with torch.manual_seed(47)
     before each generator call, as the package's picture paths do; the generator runs in the mode it is in.
@@ -180,8 +181,17 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
     polygons=True (with seg_model; ValueError without, before any launch): the outlines of the regions
     (floodgan.outline.region_outlines of the regions' labels at `connectivity`), with "flood_mask" and "regions" as
     `elevation` gives them (the minima off unless given).  The result gains "outlines".
+    drainage=True (with elevation; ValueError without, before any launch; seg_model is not needed, and without it the
+    elevation gives no depth): the drainage of the elevation (floodgan.flow.flow_accumulation with `flat_rounds`).
+    The result gains "flow" (flow_accumulation's dict) and, when the regions are computed, their table gains
+    "max_accumulation" and "pit_pixels" (floodgan.flow.flow_region_table), which "flow" also carries as "table".
     Out of scope: attention-mask mosaics, reflect-padding of scenes smaller than a window, GeoTIFF output."""
-    if elevation is not None and seg_model is None:
+    if drainage:
+        from .flow import check_flat_rounds
+        if elevation is None:
+            raise ValueError("predict_scene: drainage=True routes flow over the scene's elevation and needs elevation")
+        flat_rounds = check_flat_rounds(flat_rounds)
+    if elevation is not None and seg_model is None and not drainage:
         raise ValueError("predict_scene: elevation gives the depth of the flood mask and needs seg_model")
     if polygons and seg_model is None:
         raise ValueError("predict_scene: polygons=True outlines the regions of the flood mask and needs seg_model")
@@ -244,7 +254,7 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
                 logits = ml.result()
             res["flood_logits"] = logits
             res["flood_fraction"] = int(ops.flood_count(logits).cpu()) / (H * W)
-            if sieve or elevation is not None or polygons:
+            if sieve or elevation is not None or polygons:          # (drainage comes with an elevation)
                 from .regions import flood_regions
                 regions = flood_regions(logits, "logit", min_region, min_hole, connectivity)     # (1, 0: no sieve)
                 res["flood_mask"] = regions.pop("mask")
@@ -259,6 +269,21 @@ def predict_scene(generator, x, tile=512, overlap=64, batch=8, seg_model=None, b
             if polygons:
                 from .outline import region_outlines
                 res["outlines"] = region_outlines(res["regions"]["labels"], connectivity)
+        if drainage:
+            add_drainage(res, elevation, flat_rounds)
+    return res
+
+
+def add_drainage(res, elevation, flat_rounds=0):
+    """predict_scene's drainage=True on a result `res` of it: "flow" (floodgan.flow.flow_accumulation of the elevation
+    with flat_rounds) and, when res holds regions, their table's "max_accumulation" and "pit_pixels", which "flow"
+    also carries as "table".  Returns res."""
+    from .flow import flow_accumulation, flow_region_table
+    flow = flow_accumulation(elevation.contiguous(), flat_rounds=flat_rounds)
+    if "regions" in res:
+        flow["table"] = flow_region_table(flow, res["regions"])
+        res["regions"]["table"].update(flow["table"])
+    res["flow"] = flow
     return res
 
 

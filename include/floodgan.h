@@ -863,6 +863,58 @@ int fg_outline_vertices(const int* key, const int* ring, const int* corners, con
                         const int* base, int H, int W, int E, int V, int* vertices, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------- */
+/* flow routing: D8 directions, flats, accumulation / basin / length (not in the reference) */
+/* ---------------------------------------------------------------------------------------- */
+/* Pixel indices are i = y * W + x as for the regions.  A pixel of the elevation (contiguous fp32 [H, W]) is DATA when
+ * its value is finite, NODATA otherwise; what lies outside the scene is never a neighbour.  The neighbour codes are
+ * k = 0 .. 7 = E, SE, S, SW, W, NW, N, NE, (dy, dx) = (0, 1), (1, 1), (1, 0), (1, -1), (0, -1), (-1, -1), (-1, 0),
+ * (-1, 1).  A direction plane is contiguous uint8 [H, W]: 0 .. 7 the neighbour a pixel drains to, 8 a PIT (a data
+ * pixel that drains nowhere), 255 nodata.  Every entry fails with FG_ERR_INVALID and writes nothing on a null pointer
+ * it needs, a size that is not positive or too large (H * W >= 2^31), a misaligned pointer or a round count out of
+ * range.  Indices the kernels read from device memory (receivers, ancestors, labels, ranks) are checked against the
+ * plane or table they index before use.
+ *
+ * fg_flow_directions: steepest descent.  For a data pixel p and each data neighbour n_k inside the scene, d_k =
+ * z[p] - z[n_k] in fp32; only d_k > 0 qualifies; the key is c_k (double) d_k (double) d_k with c_k = 2 for a cardinal
+ * (even) k and 1 for a diagonal one -- the squares of d / 1 and d / sqrt(2), exact in fp64 -- and p takes the k of the
+ * largest key, among equal keys the smallest k; 8 when none qualifies.  One launch, one lane per pixel, plain loads.
+ *
+ * fg_flow_flats: `rounds` (0 .. 32768) rounds of the breadth-first wave that drains flats towards their outlets.  In
+ * a round, a pixel that is a pit in the previous round's plane takes the direction of its first neighbour, in the
+ * order 0, 2, 4, 6, 1, 3, 5, 7, that is inside the scene, has exactly its elevation and a code 0 .. 7 in the previous
+ * round's plane; every other pixel keeps its code.  dir_in holds the plane to start from and is used as the second
+ * buffer (its contents after the call are unspecified); the result lands in dir_out, which must be another plane.
+ * counts (int32 [rounds], may be null for 0 rounds) is cleared and counts[r] becomes the number of pixels directed
+ * in round r + 1.  `rounds` launches whatever the data, and at most one copy.
+ *
+ * fg_flow_accumulate, from a direction plane: the RECEIVER of a pixel with code k = 0 .. 7 is its neighbour k; a code
+ * that is neither 0 .. 8 nor 255, a neighbour outside the scene and a neighbour that is nodata make the pixel a pit.
+ *   acc[p]     the number of data pixels whose path passes through p, itself included; 0 on nodata
+ *   basin[p]   the index of the pit p's path ends in (a pit names itself); -1 on nodata
+ *   length[p]  the number of steps to that pit (0 at the pit); -1 on nodata
+ * all contiguous int32 [H, W] and distinct.  Pointer doubling with scatter, K = fg_flow_rounds(H, W) =
+ * ceil(log2 max(H W, 2)) rounds whatever the data: one launch for the receivers, then per round one copy of the
+ * accumulation and one launch, 2 K + 1 in all.  A round reads one set of buffers and writes the other; its only
+ * atomics are relaxed int32 adds, so two calls give the same bits.  No workgroup waits for another.  A direction
+ * plane whose receivers form a cycle (steepest descent and the flat wave never make one) is followed for 2^K steps:
+ * the values on it and upstream of it are unspecified, and nothing outside the planes is touched.
+ * scratch: fg_flow_scratch_bytes(H, W) bytes of device memory (5 int32 planes, 20 bytes per pixel), 8-byte aligned,
+ * the caller's -- the library allocates nothing; both helpers return 0 for sizes the entry refuses.
+ *
+ * fg_flow_region_table, with the labels / rank protocol of fg_regions_table: table (contiguous int64 [R, 2]) row r
+ * becomes {max_accumulation, pit_pixels} of the component of rank r: the maximum of acc over its pixels and the number
+ * of its pixels whose direction code is 8.  The whole table is cleared first.  int64 atomic max and add only. */
+int fg_flow_rounds(int H, int W);
+long long fg_flow_scratch_bytes(int H, int W);
+int fg_flow_directions(const float* elev, int H, int W, unsigned char* dir, hipStream_t stream);
+int fg_flow_flats(const float* elev, int H, int W, unsigned char* dir_in, unsigned char* dir_out, int rounds,
+                  int* counts, hipStream_t stream);
+int fg_flow_accumulate(const unsigned char* dir, int H, int W, int* acc, int* basin, int* length, void* scratch,
+                       hipStream_t stream);
+int fg_flow_region_table(const int* labels, const int* rank, const int* acc, const unsigned char* dir, int H, int W,
+                         long long* table, int R, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------- */
 /* tile data path                                                    */
 /* ---------------------------------------------------------------------------------------- */
 /* Host-side baseline TIFF decode, replacing tifffile.imread (models/data.py:64-68) for the files
